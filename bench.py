@@ -30,7 +30,11 @@ timed region includes the three-stream pipeline's fill and its drain (the
 last step's tally); over 20 steps that fixed ~2.4 ms is 7 % of the region
 (DESIGN.md §5, round 6).
 
-Prints ONE JSON line on rank 0, with:
+A plain run sets up, warms up, times the steps and prints ONE JSON line on
+rank 0 (metric, value, unit, ms_per_step, the step's verdict histogram and
+tally sizes, the cold first batch).  --dump-outputs DIR also writes the last
+timed step's outputs as .npy files (dump_outputs).  --full adds, after the
+timed region and on the same line:
   roofline      the dominant kernel (k_fast_sums) timed live with HIP events
                 on the library's stream (hd_ctx_profile), its algorithmic
                 int32 work per message, and the verify call as a whole;
@@ -108,6 +112,13 @@ def parse(argv=None):
     ap.add_argument("--sub-steps", type=int, default=100)
     ap.add_argument("--no-c4-check", action="store_true",
                     help="skip the untimed full-size bit-exact check of a 16M 30 %% adversarial C4 batch")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the roofline pass, the oracle sample check, the side measurements, "
+                         "the CPU baseline, the sub-benchmarks and the 16M C4 check (each still subject to its "
+                         "--no-* flag); without it only the headline is set up, warmed, timed and printed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (verdict, recovered signatory, valid bitmap, tally "
+                         "rows) as DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--dist-backend", default="nccl",
                     help="nccl (= RCCL, one GPU per rank) or gloo: a rehearsal of the N > 1 path with ranks "
                          "sharing the visible GPUs and host-side collectives")
@@ -637,6 +648,45 @@ def timed(pipe, steps, dist, dev):
     return time.perf_counter() - t
 
 
+DUMP_BUDGET = {"recovered": 32 << 20, "verdict": 8 << 20, "tally_dup": 8 << 20, "bitmap": 4 << 20,
+               "tally_counts": 4 << 20, "tally_hr": 4 << 20}       # bytes on disk per output, 60 MB in all
+
+
+def dump_outputs(path, pipe, steps, rank, world):
+    """--dump-outputs: what the last timed step handed its caller, as
+    DIR/<name>.npy (rank r of N > 1: <name>_rank<r>.npy, its shard's).
+    verdict [B], recovered [B, 32] and tally_dup [B] (byte values) as float32;
+    bitmap [B / 32] (the 32-bit words, unsigned) and the tally's rows
+    tally_counts [k, 5] / tally_hr [m, 6] (shard.COUNT_COLS / HR_COLS) as
+    float64, all exact.  An output over its share of DUMP_BUDGET (divided by
+    the ranks) is cut to a seeded sample of its rows, the same rows in every
+    run with the same arguments (recovered at 1M messages: 262,144 rows)."""
+    import numpy as np
+    from hyperdrive_amd.shard import pack_tally
+    verdict, recovered, bitmap = pipe.last(steps)
+    arrays = {"verdict": verdict.cpu().numpy().astype(np.float32),
+              "recovered": recovered.cpu().numpy().astype(np.float32),
+              "bitmap": bitmap.cpu().numpy().view(np.uint32).astype(np.float64)}
+    last = pipe.last_tally
+    if isinstance(last, tuple):                  # one GPU: the library's output struct and its arrays
+        t, a = last
+        last = pack_tally(a, t.n_counts, t.n_hr)
+        if t.dup:
+            arrays["tally_dup"] = a["dup"][:pipe.B].astype(np.float32)
+    if last is not None:
+        arrays["tally_counts"] = last["counts"].astype(np.float64)
+        arrays["tally_hr"] = last["hr"].astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        row = max(1, arr.nbytes // max(1, arr.shape[0]))
+        keep = DUMP_BUDGET[name] // world // row
+        if arr.shape[0] > keep:
+            seed = 1000 + list(DUMP_BUDGET).index(name)
+            rows = np.sort(np.random.default_rng(seed).choice(arr.shape[0], keep, replace=False))
+            arr = arr[rows]
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), arr)
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -731,19 +781,22 @@ def main():
     if pipe.host_trace:
         t0h = pipe.host_trace[0][2]
         print("host trace:", [(a, k, round((t - t0h) * 1e3, 3)) for a, k, t in pipe.host_trace], file=sys.stderr)
-    # Roofline pass (untimed for `value`): the same steps with one verify
-    # stream, so that every k_fast_sums launch and verify call runs alone and
-    # its HIP-event duration is its own (in the timed region consecutive calls
-    # overlap and share the CUs)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pipe, args.steps, rank, world)
     all_streams = pipe.wss
-    pipe.wss = pipe.wss[:1]
-    torch.cuda.synchronize(dev)
-    v.profile(True)
-    v.profile_read()                    # clear
-    prof_s = timed(pipe, args.steps, dist, dev)
-    calls, verify_ms, sums_launches, sums_ms = v.profile_read()
-    v.profile(False)
-    pipe.wss = all_streams
+    if args.full:
+        # Roofline pass (untimed for `value`): the same steps with one verify
+        # stream, so that every k_fast_sums launch and verify call runs alone and
+        # its HIP-event duration is its own (in the timed region consecutive calls
+        # overlap and share the CUs)
+        pipe.wss = pipe.wss[:1]
+        torch.cuda.synchronize(dev)
+        v.profile(True)
+        v.profile_read()                    # clear
+        prof_s = timed(pipe, args.steps, dist, dev)
+        calls, verify_ms, sums_launches, sums_ms = v.profile_read()
+        v.profile(False)
+        pipe.wss = all_streams
     own_elapsed = elapsed
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev if args.dist_backend == "nccl" else "cpu")
@@ -788,14 +841,6 @@ def main():
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
         value = total * args.steps / elapsed
-        geom = v.fastpath_geometry()
-        w_fast = fast_ops_per_msg(*geom)
-        w_sums = sums_ops_per_msg(geom[0], geom[1])
-        live = B - fallback                      # messages of a step through the known-key check
-        sums_avg = sums_ms / max(sums_launches, 1)
-        call_avg = verify_ms / max(calls, 1)
-        w_call = (live * w_fast + fallback * W_OPS_PER_MSG) / B
-        achieved = live * w_sums / (sums_avg * 1e-3)
         out = {
             "metric": "verified consensus msgs/sec (secp256k1) at 1/2/4/8 MI355X; % INT32 VALU peak",
             "value": value,
@@ -820,7 +865,30 @@ def main():
                                        f"to their owner (all-to-all); count rows all-gathered; backend "
                                        f"{'RCCL' if args.dist_backend == 'nccl' else args.dist_backend}"
                                        if world > 1 else "one GPU")},
-            "roofline": {
+            "verdicts": hist,
+            "tally": pipe.tally_info,
+            "tally_thread_ms": {"mean": sum(timed_tally_ms) / len(timed_tally_ms), "max": max(timed_tally_ms),
+                                "note": "host wall time of each step's tally on its thread, from its start (queued behind its "
+                                        "verification, whose end it waits for) to its results on the host (beside the next "
+                                        "verifications), timed region only"},
+            "cold": {"first_batch_s": cold_s, "cold_msgs_per_s": total / cold_s,
+                     "ctx_create_s": ctx_s, "cold_msgs_per_s_incl_ctx": total / (cold_s + ctx_s),
+                     "note": "first batch on a fresh context: full recovery of every message, key learning and "
+                             "the per-key table build; ctx_create_s builds the shared G table"},
+            "gen_s": gen_s,
+            "verify_streams": len(all_streams),
+            "tally_mode": "async" if pipe.async_tally else "thread", "tally_retries": pipe.tally_retries,
+        }
+        if args.full:
+            geom = v.fastpath_geometry()
+            w_fast = fast_ops_per_msg(*geom)
+            w_sums = sums_ops_per_msg(geom[0], geom[1])
+            live = B - fallback                      # messages of a step through the known-key check
+            sums_avg = sums_ms / max(sums_launches, 1)
+            call_avg = verify_ms / max(calls, 1)
+            w_call = (live * w_fast + fallback * W_OPS_PER_MSG) / B
+            achieved = live * w_sums / (sums_avg * 1e-3)
+            out["roofline"] = {
                 "bound": "valu",
                 "kernel": "k_fast_sums (the known-key check's mixed additions; dominant kernel of the verify call)",
                 "achieved": achieved / 1e12,
@@ -848,27 +916,13 @@ def main():
                 },
                 "geometry": {"g_windows": geom[0], "key_windows": geom[1], "msgs_per_inversion": geom[2]},
                 "fallback_msgs_last_step": fallback, "known_signatories": known,
-            },
-            "verdicts": hist,
-            "tally": pipe.tally_info,
-            "tally_thread_ms": {"mean": sum(timed_tally_ms) / len(timed_tally_ms), "max": max(timed_tally_ms),
-                                "note": "host wall time of each step's tally on its thread, from its start (queued behind its "
-                                        "verification, whose end it waits for) to its results on the host (beside the next "
-                                        "verifications), timed region only"},
-            "cold": {"first_batch_s": cold_s, "cold_msgs_per_s": total / cold_s,
-                     "ctx_create_s": ctx_s, "cold_msgs_per_s_incl_ctx": total / (cold_s + ctx_s),
-                     "note": "first batch on a fresh context: full recovery of every message, key learning and "
-                             "the per-key table build; ctx_create_s builds the shared G table"},
-            "gen_s": gen_s,
-            "one_stream_msgs_per_s": total * args.steps / prof_s,
-            "verify_streams": len(all_streams),
-            "tally_mode": "async" if pipe.async_tally else "thread", "tally_retries": pipe.tally_retries,
-        }
+            }
+            out["one_stream_msgs_per_s"] = total * args.steps / prof_s
         if per_rank is not None:
             out["dist_backend"] = args.dist_backend
             out["per_rank"] = per_rank
             out["distinct_devices"] = len({p["device"] for p in per_rank})
-        if world == 1:
+        if world == 1 and args.full:
             out["oracle_sample_check"] = oracle_sample_check(db, verdict, recovered, sigs)
             if not args.no_aux:
                 try:
