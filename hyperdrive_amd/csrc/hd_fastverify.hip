@@ -35,6 +35,7 @@
 
 #include "../../include/hd_verify.h"
 #include "hd_fixedbase.h"
+#include "hd_dedup.h"
 #include "hd_scmont.h"
 #include "hd_internal.h"
 #include "hd_verify_msg.h"
@@ -66,11 +67,16 @@ struct FbWork {
     // call's inversion kernels (n / K lanes), the last partial round of its
     // k_fast_sums and its fallback recovery leave idle.
     struct Scratch {
-        uint32_t* rows = nullptr;     // the split check's per-message rows (SplitRows, 62 words per message)
+        uint32_t* rows = nullptr;     // the split check's per-message rows (SplitRows, 63 words per message)
         size_t cap_rows = 0;
+        uint32_t* dtab = nullptr;     // the repeat table (hd_dedup.h): dd_table_words(n) message indices
+        size_t cap_dtab = 0;
         uint32_t* slow = nullptr;     // message index list: the known-key check's leftovers
         size_t cap_slow = 0;
-        uint32_t* count = nullptr;    // its length (device words: [0] leftovers, [1] after k_slow_lift)
+        // device words: [0] leftovers (slow's length), [1] after k_slow_lift,
+        // [2] distinct live messages (the compact slots in use), [3] repeats;
+        // [2] and [3] are one 64-bit word to k_fast_prep's atomic
+        uint32_t* count = nullptr;
         uint32_t* slow2 = nullptr;    // the leftovers that pass the lift: the full recovery's list
         size_t cap_slow2 = 0;
         hipEvent_t done = nullptr;    // recorded after the last call that used this set
@@ -95,8 +101,14 @@ struct FbWork {
     // sized by the last list instead of the batch keeps ~2,000 blocks that
     // would only start and exit from queueing for SIMD slots behind a
     // concurrent call's k_fast_sums).  UINT32_MAX = none seen yet.
+    // [2], [3]: the distinct live messages and the batch size of the latest
+    // call (k_fast_sinv stores them); their ratio picks the next calls'
+    // messages per inversion (split_k_for).
     uint32_t* est_host = nullptr;
     uint32_t* est_dev = nullptr;
+    // hd_ctx_dedup_stats: [0] messages that entered the known-key check, [1]
+    // those served as repeats, since context creation (device, 64-bit)
+    unsigned long long* dstats = nullptr;
     // Ordering between calls (hd_fb_verify): a call waits (on the device) for
     // the last call that used its scratch set.  While keys can still be
     // learned (nr_host != 0), or on the first call after the last key became
@@ -204,16 +216,44 @@ HD void soa_store(uint32_t* __restrict__ p, uint32_t n, uint32_t i, const uint32
     HD_UNROLL for (int k = 0; k < NW; k++) p[(size_t)k * n + i] = w[k];
 }
 
+//
+// Repeats and compaction (hd_dedup.h).  k_fast_prep gives every
+// distinct live message a compact slot c from a device counter and writes its
+// rows at c (all rows keep the batch's stride n); a vote that repeats an
+// earlier live vote of the batch byte for byte takes no slot.  ref[i] names
+// message i's slot, the message it repeats, or its early code (dd_resolve).
+// The three middle kernels run over slots [0, live), live read from the
+// counter: their grids are sized for n and the surplus waves exit at once;
+// the inversion kernels derive T from live, so their waves are full.
+// k_fast_cmp stays one lane per message in index order (the bitmap ballot):
+// lane i resolves its slot through ref and compares from that slot's rows, so
+// every copy of a repeated message gets the outputs its own check would give.
+// Which of two equal messages claims the slot, and the order of the compact
+// slots, vary from run to run; no output depends on either.
 struct SplitRows {
-    uint32_t* aux;   // n: slot << 8 | code
-    int32_t* idx;    // n: admitted (sorted) index
-    uint32_t* u1;    // 8n: m
-    uint32_t* u2;    // 8n: r
-    uint32_t* s;     // 8n: s
-    uint32_t* pre;   // 9n: prefix products of s, then s^-1 R (radix 2^29); later of Z, then Z^-1
-    uint32_t* xyz;   // 27n: the XYZZ sum as (X ZZZ, Y ZZ, Z = ZZ ZZZ) (gxz_finish)
+    uint32_t* aux;   // n, by slot: table slot << 8 | code
+    int32_t* idx;    // n, by message: admitted (sorted) index
+    uint32_t* ref;   // n, by message: compact slot | HD_DD_REPEAT + message | HD_DD_FINAL + code
+    uint32_t* u1;    // 8n, by slot: m
+    uint32_t* u2;    // 8n, by slot: r
+    uint32_t* s;     // 8n, by slot: s
+    uint32_t* pre;   // 9n, by slot: prefix products of s, then s^-1 R (radix 2^29); later of Z, then Z^-1
+    uint32_t* xyz;   // 27n, by slot: the XYZZ sum as (X ZZZ, Y ZZ, Z = ZZ ZZZ) (gxz_finish)
+    uint32_t* cnt;   // Scratch::count: [2] live slots, [3] repeats of this call
     int prio;        // wave priority of the short kernels (HD_VAR_WAVE_PRIO)
 };
+
+// the code of message i and, when it has rows, its compact slot (two loads
+// for a repeat; valid after k_fast_prep's kernel boundary)
+HD uint32_t dd_resolve(const SplitRows& rows, uint32_t i, uint32_t& c, bool& has_slot) {
+    uint32_t rf = rows.ref[i];
+    has_slot = (rf >> 30) != 3u;
+    c = 0;
+    if (!has_slot) return rf & 0xFFu;
+    if (rf & HD_DD_REPEAT) rf = rows.ref[rf & HD_DD_INDEX];
+    c = rf;
+    return rows.aux[c] & 0xFFu;
+}
 
 // s_setprio takes an immediate: a uniform branch per level
 HD void wave_prio(int p) {
@@ -241,16 +281,19 @@ __global__ __launch_bounds__(256) void k_fast_prep(DevBatch b, const uint8_t* __
                                                    const uint32_t* __restrict__ state,
                                                    const int32_t* __restrict__ adm_slot, AdmIndex ix,
                                                    uint32_t n_adm, SplitRows rows, const uint32_t* __restrict__ fdict,
-                                                   uint32_t* __restrict__ fhit, uint32_t fbase) {
+                                                   uint32_t* __restrict__ fhit, uint32_t fbase,
+                                                   uint32_t* __restrict__ dtab, uint32_t dmask) {
     wave_prio(rows.prio);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t n = b.n;
-    if (i >= n) return;
-    FastSrc src{b, i, digest_in};
-    const uint32_t type = src.type();
-    uint32_t code = HD_NEEDS_SLOW, slot = 0;
+    const bool present = i < n;   // (no early exit: the block's lanes meet at the slot counter below)
+    FastSrc src{b, present ? i : 0u, digest_in};
+    const uint32_t type = present ? src.type() : 0u;
+    uint32_t code = HD_NEEDS_SLOW, slot = 0, rep = HD_DD_EMPTY;
     int32_t idx = -1;
-    if (type < 1 || type > 3) {
+    sc r, s, m;
+    if (!present) {
+    } else if (type < 1 || type > 3) {
         code = V_BAD_TYPE;
     } else {
         uint32_t from_be[8];
@@ -267,33 +310,86 @@ __global__ __launch_bounds__(256) void k_fast_prep(DevBatch b, const uint8_t* __
             slot = (uint32_t)sl;
             if (idx == -2) atomicAdd(&fhit[sl - (int32_t)fbase], 1u);   // a foreign slot's use (fb_evict)
             FastIn in;
+            DdKey me;   // this message's inputs, as the repeat table compares them
+            me.height = me.round = 0;
             if (digest_in) {
                 load_row32_be(in.digest_be, digest_in, i);
+                HD_UNROLL for (int k = 0; k < 8; k++) me.value[k] = in.digest_be[k];
             } else {
-                uint32_t value_be[8];
-                src.value_words(value_be);
+                src.value_words(me.value);
+                me.height = b.height[i];
+                me.round = b.round[i];
                 if (type == T_PROPOSE)
-                    sha256_propose(in.digest_be, b.height[i], b.round[i], b.valid_round ? b.valid_round[i] : -1,
-                                   value_be);
+                    sha256_propose(in.digest_be, me.height, me.round, b.valid_round ? b.valid_round[i] : -1, me.value);
                 else
-                    sha256_vote(in.digest_be, b.height[i], b.round[i], value_be);
+                    sha256_vote(in.digest_be, me.height, me.round, me.value);
             }
             src.sig(in.r_be, in.s_be, in.v);
             in.ready = true;
-            sc r, s, m;
             fe x;
             uint8_t o;
             if (fast_prefix(o, r, s, m, x, in)) {
                 code = HD_FAST_LIVE;
-                soa_store(rows.u1, n, i, m.v);
-                soa_store(rows.u2, n, i, r.v);
-                soa_store(rows.s, n, i, s.v);
+                // A vote looks for an equal earlier vote (hd_dedup.h).  The
+                // table holds live votes only, so a match is a message with
+                // rows; the fields compared are the caller's input arrays,
+                // which no kernel writes, so the compare needs no ordering
+                // with the claimant's lane.  Proposes are never merged (their
+                // preimage has valid_round).  dtab is NULL with HD_VAR_DEDUP 0.
+                if (dtab && type != T_PROPOSE) {
+                    HD_UNROLL for (int k = 0; k < 8; k++) {
+                        me.from[k] = from_be[k];
+                        me.r[k] = in.r_be[k];
+                        me.s[k] = in.s_be[k];
+                    }
+                    me.v = in.v;
+                    const uint32_t h = dd_hash(me);
+                    HD_NOUNROLL for (uint32_t p = 0; p < HD_DD_PROBES; p++) {
+                        const uint32_t cur = atomicCAS(&dtab[(h + p) & dmask], HD_DD_EMPTY, i);
+                        if (cur == HD_DD_EMPTY) break;   // claimed: distinct
+                        DdKey other;
+                        dd_key_load(other, b.height, b.round, b.value32, digest_in, b.from32, b.sig65, cur, n);
+                        if (dd_key_equal(me, other)) {
+                            rep = cur;
+                            break;
+                        }
+                    }
+                }
             } else {
                 code = o;
             }
         }
     }
-    rows.aux[i] = slot << 8 | code;
+    // Compact slots: one 64-bit atomic per block adds its distinct live
+    // messages (low word, returned: the block's first slot) and its repeats
+    // (high word); a lane's slot follows from the ballots.
+    const bool live = code == HD_FAST_LIVE;
+    const bool distinct = live && rep == HD_DD_EMPTY;
+    __shared__ uint32_t s_cnt[4], s_base;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const unsigned long long bd = __ballot(distinct), br = __ballot(live && !distinct);
+    if (lane == 0) s_cnt[wv] = (uint32_t)__popcll(bd) | (uint32_t)__popcll(br) << 16;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];   // (<= 256 each half: no carry)
+        s_base = 0;
+        if (t)
+            s_base = (uint32_t)atomicAdd((unsigned long long*)(rows.cnt + 2),
+                                         (unsigned long long)(t & 0xFFFFu) | (unsigned long long)(t >> 16) << 32);
+    }
+    __syncthreads();
+    if (!present) return;
+    if (distinct) {
+        uint32_t c = s_base + (uint32_t)__popcll(bd & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wv; w++) c += s_cnt[w] & 0xFFFFu;
+        rows.aux[c] = slot << 8 | HD_FAST_LIVE;
+        soa_store(rows.u1, n, c, m.v);
+        soa_store(rows.u2, n, c, r.v);
+        soa_store(rows.s, n, c, s.v);
+        rows.ref[i] = c;
+    } else {
+        rows.ref[i] = live ? (HD_DD_REPEAT | rep) : (HD_DD_FINAL | code);
+    }
     rows.idx[i] = idx;
 }
 
@@ -305,20 +401,42 @@ __global__ __launch_bounds__(256) void k_fast_prep(DevBatch b, const uint8_t* __
 // row.  The lane's K scalars and prefixes stay in registers (both walks are
 // unrolled), and the loads of all K messages issue together up front: with
 // n / K lanes there are too few waves to hide a load per step.
+//
+// The slots in use come from k_fast_prep's counter; T, the lanes of the
+// K-per-lane kernels (a multiple of 64), follows from it in the kernel, so a
+// batch of repeats does not spread its few slots over lanes sized for n.
 template <int K>
-__global__ __launch_bounds__(256) void k_fast_sinv(uint32_t n, uint32_t T, SplitRows rows) {
+HD uint32_t split_lanes(uint32_t nc) {
+    return ((nc + (uint32_t)K - 1) / (uint32_t)K + 63u) & ~63u;
+}
+
+// (est / stats: the first lane stores the call's slot count for the host's
+// next launches and adds the call to the context's cumulative counters)
+template <int K>
+__global__ __launch_bounds__(256) void k_fast_sinv(uint32_t n, SplitRows rows, uint32_t* __restrict__ est,
+                                                   unsigned long long* __restrict__ stats) {
     wave_prio(rows.prio);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
+    if (t == 0) {
+        const uint32_t reps = rows.cnt[3];
+        if (est) {   // the call's slots, then its n (read in this order by split_k_for's share)
+            est[1] = n;
+            est[0] = nc;
+        }
+        if (nc + reps) atomicAdd(&stats[0], (unsigned long long)nc + reps);
+        if (reps) atomicAdd(&stats[1], (unsigned long long)reps);
+    }
     if (t >= T) return;
     sc sv[K];
     uint32_t live = 0;   // bit j: message j of this lane goes on
     static_for<K>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         const uint32_t i = (uint32_t)j * T + t;
-        const uint32_t ic = i < n ? i : n - 1;   // rows exist up to n - 1
+        const uint32_t ic = i < nc ? i : nc - 1;   // slots in use end at nc - 1 (T > 0: nc >= 1)
         const uint32_t a = rows.aux[ic];
         soa_load(sv[j].v, rows.s, n, ic);
-        live |= (i < n && (a & 0xFFu) == HD_FAST_LIVE) ? 1u << j : 0u;
+        live |= (i < nc && (a & 0xFFu) == HD_FAST_LIVE) ? 1u << j : 0u;
     });
     if (!live) return;
     sm pre[K], acc;
@@ -415,8 +533,10 @@ __global__ __launch_bounds__(256, WAVES) void k_fast_sums(uint32_t n, const gp* 
     constexpr int NG = FbL<HD_FB_WG>::NWIN, NT = NG + FbL<WP>::NWIN;
     static_assert(PF >= 0 && PF <= 2, "prefetch depth");
     __shared__ uint32_t sdig[NT * 256];
+    // lane i takes compact slot i; the grid is sized for n, and the waves past
+    // the slots in use exit here
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+    if (i >= rows.cnt[2]) return;
     const uint32_t a = rows.aux[i];
     if ((a & 0xFFu) != HD_FAST_LIVE) return;
     // The table pointers as global (address space 1) pointers: the loads
@@ -520,10 +640,11 @@ __global__ __launch_bounds__(256, WAVES) void k_fast_sums(uint32_t n, const gp* 
 // linear walk: its Montgomery-form tree needs more registers than a wave has
 // and spills -- measured 90 -> 100-129 us, while the tree takes zinv 76 -> 73.)
 template <int K>
-__global__ __launch_bounds__(256) void k_fast_zinv(uint32_t n, uint32_t T, SplitRows rows) {
+__global__ __launch_bounds__(256) void k_fast_zinv(uint32_t n, SplitRows rows) {
     static_assert(K >= 2 && (K & (K - 1)) == 0, "K: a power of two");
     wave_prio(rows.prio);
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
     if (t >= T) return;
     const uint32_t* zrow = rows.xyz + 18 * (size_t)n;
     fe node[2 * K];
@@ -531,11 +652,11 @@ __global__ __launch_bounds__(256) void k_fast_zinv(uint32_t n, uint32_t T, Split
     static_for<K>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
         const uint32_t i = (uint32_t)j * T + t;
-        const uint32_t ic = i < n ? i : n - 1;
+        const uint32_t ic = i < nc ? i : nc - 1;
         const uint32_t a = rows.aux[ic];
         fe z;
         soa_load(z.n, zrow, n, ic);
-        const bool on = i < n && (a & 0xFFu) == HD_FAST_LIVE;
+        const bool on = i < nc && (a & 0xFFu) == HD_FAST_LIVE;
         live |= on ? 1u << j : 0u;
         HD_UNROLL for (int k = 1; k < 9; k++) z.n[k] = on ? z.n[k] : 0u;
         z.n[0] = on ? z.n[0] : 1u;
@@ -586,15 +707,20 @@ __device__ __forceinline__ void cmp_one(const DevBatch& b, const SplitRows& rows
     const uint32_t n = b.n;
     uint8_t v = HD_NEEDS_SLOW;
     if (present) {
-        v = (uint8_t)(rows.aux[i] & 0xFFu);
+        // the rows of message i are its slot's: its own, or those of the
+        // message it repeats (same inputs, so the same comparison; a repeat
+        // redoes the two products instead of a second pass copying outputs)
+        uint32_t c;
+        bool has_slot;
+        v = (uint8_t)dd_resolve(rows, i, c, has_slot);
         if (v == HD_FAST_LIVE) {
             fe xn, yn, w, x;
-            soa_load(xn.n, rows.xyz, n, i);
-            soa_load(yn.n, rows.xyz + 9 * (size_t)n, n, i);
+            soa_load(xn.n, rows.xyz, n, c);
+            soa_load(yn.n, rows.xyz + 9 * (size_t)n, n, c);
             if (zi) w = *zi;
-            else soa_load(w.n, rows.pre, n, i);
+            else soa_load(w.n, rows.pre, n, c);
             sc r;
-            soa_load(r.v, rows.u2, n, i);
+            soa_load(r.v, rows.u2, n, c);
             const uint32_t sv = b.sig65[65 * (size_t)i + 64];
             fast_rx(x, r, sv);
             v = fast_final_xz(xn, yn, w, x, sv);
@@ -693,14 +819,19 @@ __global__ __launch_bounds__(256) void k_slow_lift(DevBatch b, const uint32_t* _
                 fe_add(y2, y2, seven);
                 if (!fe_sqrt(y, y2)) {
                     pre = V_NO_POINT;
-                } else if (gtab && rows.aux && (rows.aux[i] & 0xFFu) == HD_FAST_LIVE) {
-                    ge R;
-                    R.x = x;
-                    R.y = y;
-                    if (fe_is_odd(y) != ((v & 1u) != 0)) fe_neg(R.y, y);
-                    sc m;   // (s is sig_prefix's; m as k_fast_prep left it)
-                    soa_load(m.v, rows.u1, b.n, i);
-                    if (fb_is_infinity<HD_FB_WG>(m, s, R, GpTab{gtab})) pre = V_INFINITY;
+                } else if (gtab && rows.aux) {
+                    // (a repeat on the list reads its m at the slot of the message it repeats)
+                    uint32_t c;
+                    bool has_slot;
+                    if (dd_resolve(rows, i, c, has_slot) == HD_FAST_LIVE) {
+                        ge R;
+                        R.x = x;
+                        R.y = y;
+                        if (fe_is_odd(y) != ((v & 1u) != 0)) fe_neg(R.y, y);
+                        sc m;   // (s is sig_prefix's; m as k_fast_prep left it)
+                        soa_load(m.v, rows.u1, b.n, c);
+                        if (fb_is_infinity<HD_FB_WG>(m, s, R, GpTab{gtab})) pre = V_INFINITY;
+                    }
                 }
             }
             keep = pre == V_VALID;
@@ -1198,12 +1329,14 @@ int hd_fb_init(hd_ctx* ctx) {
     FBCHK(hipHostMalloc((void**)&f->nr_host, 4, hipHostMallocMapped | hipHostMallocCoherent), "fb ready count");
     *f->nr_host = 0xFFFFFFFFu;
     FBCHK(hipHostGetDevicePointer((void**)&f->nr_dev, f->nr_host, 0), "fb ready count map");
-    FBCHK(hipHostMalloc((void**)&f->est_host, 8, hipHostMallocMapped | hipHostMallocCoherent), "fb list estimate");
-    f->est_host[0] = f->est_host[1] = 0xFFFFFFFFu;
+    FBCHK(hipHostMalloc((void**)&f->est_host, 16, hipHostMallocMapped | hipHostMallocCoherent), "fb list estimate");
+    f->est_host[0] = f->est_host[1] = f->est_host[2] = f->est_host[3] = 0xFFFFFFFFu;
     FBCHK(hipHostGetDevicePointer((void**)&f->est_dev, f->est_host, 0), "fb list estimate map");
     FBCHK(hipHostMalloc((void**)&f->fpend_host, 8, hipHostMallocMapped | hipHostMallocCoherent), "fb foreign claims");
     f->fpend_host[0] = f->fpend_host[1] = 0;
     FBCHK(hipHostGetDevicePointer((void**)&f->fpend_dev, f->fpend_host, 0), "fb foreign claims map");
+    FBCHK(hipMalloc(&f->dstats, 16), "fb repeat counters");
+    FBCHK(hipMemset(f->dstats, 0, 16), "fb repeat counters clear");   // (blocking: calls on any stream add to it)
     int rc = fb_alloc_slots(ctx);
     if (rc) return rc;
     return fb_g_table(ctx, &f->gtab);
@@ -1220,11 +1353,11 @@ void hd_fb_release(hd_ctx* ctx) {
     for (hipEvent_t e : f->ev_sums) (void)hipEventDestroy(e);
     for (auto& sc : f->sc) {
         if (sc.done) (void)hipEventDestroy(sc.done);
-        void* sp[] = {sc.rows, sc.slow, sc.count, sc.slow2};
+        void* sp[] = {sc.rows, sc.slow, sc.count, sc.slow2, sc.dtab};
         for (void* p : sp)
             if (p) (void)hipFree(p);
     }
-    void* ptrs[] = {f->counts, f->adm_slot, f->zr, f->fdict, f->fnext, f->fhit, f->fkey};
+    void* ptrs[] = {f->counts, f->adm_slot, f->zr, f->fdict, f->fnext, f->fhit, f->fkey, f->dstats};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (f->nr_host) (void)hipHostFree(f->nr_host);
@@ -1235,17 +1368,33 @@ void hd_fb_release(hd_ctx* ctx) {
 }
 
 // Messages per inversion of the known-key check (HD_VAR_SPLIT_K): 8 or 16;
-// -1 (default) by batch size: 16 from 2^20 - 2^16 messages up (65,536 lanes,
-// one wave per SIMD), else 8.  The inversion kernels are bound by their
+// -1 (default) by size: 16 from 2^19 expected slots up, else 8 (before
+// round 7: from 2^20 - 2^16 messages up, 65,536 lanes, one wave per SIMD).  The inversion kernels are bound by their
 // dependent ALU chains; halving the inversions outweighs the lost second wave
 // per SIMD (1M C2 messages, one box, scalars and prefixes in registers:
 // k_fast_sinv 102 -> 91 us, k_fast_zinv 91 -> 76 us from K = 8 to 16; with the
 // rows in HBM between steps K = 4 / 8 / 16 gave 177 / 111 / 90 and 166 / 102
 // / 85 us)
+// The lanes are the distinct live messages, not the batch (repeats take no
+// slot).  The rule looks at this call's n times the slot share of the latest
+// finished call (its slots and its n, which k_fast_sinv stores into pinned
+// memory: no host sync), so a call of another size after it is still judged
+// by its own size.  Any K is correct; a stale share only picks the other one.
+// Before any call has finished the share is 1.
 static int split_k_for(const hd_ctx* ctx, uint32_t n) {
     const int k = ctx->var[HD_VAR_SPLIT_K];
     if (k > 0) return k;
-    return n >= (1u << 20) - (1u << 16) ? 16 : 8;
+    uint64_t lanes = n;
+    if (const volatile uint32_t* est = ctx->fb->est_host) {
+        const uint32_t seen = est[2], of = est[3];
+        // (a call in which nothing entered the check -- keys still unknown -- says nothing about the share)
+        if (seen != 0xFFFFFFFFu && of != 0xFFFFFFFFu && seen != 0 && seen <= of) lanes = (uint64_t)n * seen / of;
+    }
+    // Round 7, C2 with repeats merged (~623k slots, 609 waves at K = 16): K = 16
+    // 1,063 M msgs/s against 1,044-1,048 M at K = 8, so the rule's threshold
+    // came down from 2^20 - 2^16 to 2^19 slots; C3's 128k messages measured
+    // K = 8 faster (round 6), and nothing between the two has been measured.
+    return lanes >= (1u << 19) ? 16 : 8;
 }
 
 // Per-key window width for an admitted set of m: the widest tables
@@ -1495,17 +1644,20 @@ static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest
                          const FbWork::Scratch& sc, hipStream_t s, bool auth) {
     FbWork* f = ctx->fb;
     const uint32_t n = b.n;
-    // lanes of the K-per-lane kernels, a multiple of 64 (k_fast_final's bitmap words)
-    const uint32_t T = ((n + (uint32_t)K - 1) / (uint32_t)K + 63u) & ~63u;
-    const uint32_t tb = (T + 255) / 256, nb = (n + 255) / 256;
+    // The middle kernels run over the slots in use, which only the device
+    // knows: their grids cover n slots and the surplus waves exit at once.
+    const uint32_t tb = (split_lanes<K>(n) + 255) / 256, nb = (n + 255) / 256;
+    // HD_VAR_DEDUP 0: no table, so no message is ever marked a repeat; slots,
+    // ref and every kernel are the same
+    uint32_t* dtab = ctx->var[HD_VAR_DEDUP] ? sc.dtab : nullptr;
     k_fast_prep<<<nb, 256, 0, s>>>(b, d_digest, f->state, f->adm_slot, hd_adm_index(ctx), ctx->n_adm, rows,
-                                   f->fcap ? f->fdict : nullptr, f->fhit, f->fbase);
-    k_fast_sinv<K><<<tb, 256, 0, s>>>(n, T, rows);
+                                   f->fcap ? f->fdict : nullptr, f->fhit, f->fbase, dtab, dd_table_words(n) - 1u);
+    k_fast_sinv<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
     hipEvent_t* pe = fb_prof_pair(f->ev_sums, f->n_sums, f->prof);
     if (pe) (void)hipEventRecord(pe[0], s);
     launch_sums<WP>(ctx, nb, s, n, f->gtab, f->tabs, rows);
     if (pe) (void)hipEventRecord(pe[1], s);
-    k_fast_zinv<K><<<tb, 256, 0, s>>>(n, T, rows);
+    k_fast_zinv<K><<<tb, 256, 0, s>>>(n, rows);
     // whole blocks of 256: every wavefront's 64 messages are one bitmap word pair
     k_fast_cmp<<<nb, 256, 0, s>>>(b, rows, ctx->d_adm_perm, d_verdict, d_rec32, d_signer, sc.slow, sc.count,
                                   d_bitmap, auth);
@@ -1523,7 +1675,7 @@ int hd_fb_verify(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_
     f->next = (j + 1) % FbWork::NSCRATCH;
     FbWork::Scratch& sc = f->sc[j];
     if (!sc.done) FBCHK(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming), "fb scratch event");
-    if (!sc.count) FBCHK(hipMalloc(&sc.count, 8), "fb scratch count");
+    if (!sc.count) FBCHK(hipMalloc(&sc.count, 16), "fb scratch count");
     // foreign slots re-keyed (fb_evict; it waited for every earlier call)
     bool evicted = false;
     int re = fb_evict(ctx, &evicted);
@@ -1568,12 +1720,22 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
     const uint32_t blocks = (b.n + 255) / 256;
     rc = hd_dev_grow(ctx, (void**)&sc.slow2, &sc.cap_slow2, 4 * (size_t)b.n);
     if (rc) return rc;
-    FBCHK(hipMemsetAsync(sc.count, 0, 8, s), "fb count reset");
+    FBCHK(hipMemsetAsync(sc.count, 0, 16, s), "fb count reset");
     if (ctx->n_adm > 0 && f->adm_slot && f->map_ok) {
-        const size_t row_words = 62;   // per message
+        if (b.n > HD_DD_MAX_N) {   // ref's encoding (hd_dedup.h); the rows of such a batch exceed the device anyway
+            ctx->last_error = "known-key check: more than 2^30 messages in one call";
+            return HD_EINVAL;
+        }
+        const size_t row_words = 63;   // per message
         rc = hd_dev_grow(ctx, (void**)&sc.rows, &sc.cap_rows, 4 * row_words * (size_t)b.n);
         if (rc) return rc;
         const uint32_t n = b.n;
+        if (ctx->var[HD_VAR_DEDUP]) {
+            const size_t tab_bytes = 4 * (size_t)dd_table_words(n);
+            rc = hd_dev_grow(ctx, (void**)&sc.dtab, &sc.cap_dtab, tab_bytes);
+            if (rc) return rc;
+            FBCHK(hipMemsetAsync(sc.dtab, 0xFF, tab_bytes, s), "fb repeat table clear");
+        }
         SplitRows rows;
         rows.aux = sc.rows;
         rows.idx = (int32_t*)(sc.rows + (size_t)n);
@@ -1582,6 +1744,8 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
         rows.s = sc.rows + 18 * (size_t)n;
         rows.pre = sc.rows + 26 * (size_t)n;
         rows.xyz = sc.rows + 35 * (size_t)n;
+        rows.ref = sc.rows + 62 * (size_t)n;
+        rows.cnt = sc.count;
         rows.prio = ctx->var[HD_VAR_WAVE_PRIO];
         const int k = split_k_for(ctx, n);
         f->last_k = k;
@@ -1737,6 +1901,21 @@ int hd_ctx_fastpath_stats(hd_ctx* ctx, uint32_t* known_keys, uint32_t* last_fall
     }
     if (last_fallback && f->last_set >= 0)
         FBCHK(hipMemcpy(last_fallback, f->sc[f->last_set].count, 4, hipMemcpyDeviceToHost), "fallback read");
+    return HD_OK;
+}
+
+int hd_ctx_dedup_stats(hd_ctx* ctx, uint64_t* checked, uint64_t* repeats) {
+    if (!ctx) return HD_EINVAL;
+    if (checked) *checked = 0;
+    if (repeats) *repeats = 0;
+    if (!ctx->fb || !ctx->fb->dstats) return HD_OK;
+    (void)hipSetDevice(ctx->device);
+    int rq = hd_ctx_quiesce(ctx);
+    if (rq) return rq;
+    unsigned long long st[2] = {0, 0};
+    FBCHK(hipMemcpy(st, ctx->fb->dstats, 16, hipMemcpyDeviceToHost), "repeat counters read");
+    if (checked) *checked = st[0];
+    if (repeats) *repeats = st[1];
     return HD_OK;
 }
 

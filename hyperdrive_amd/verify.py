@@ -224,7 +224,7 @@ class Verifier:
 
     # include/hd_verify.h HD_VAR_*: kernel variants of this context
     VARIANTS = {"verify_waves": 0, "sum_waves": 1, "sum_prefetch": 2, "split_k": 4, "recover_g": 5,
-                "key_width": 7, "wave_prio": 8, "foreign_keys": 10, "slow_lift": 11}
+                "key_width": 7, "wave_prio": 8, "foreign_keys": 10, "slow_lift": 11, "dedup": 12}
 
     def set_variant(self, name: str, value: int) -> None:
         """Select a compiled kernel variant (A/B, variant tests); see
@@ -269,6 +269,14 @@ class Verifier:
         self._check(self._lib.hd_ctx_foreign_stats(self._ctx, ctypes.byref(r), ctypes.byref(e), ctypes.byref(c)),
                     "hd_ctx_foreign_stats")
         return (int(r.value), int(e.value), int(c.value)) if checks else (int(r.value), int(e.value))
+
+    def dedup_stats(self) -> Tuple[int, int]:
+        """(messages that entered the known-key check, those of them served as
+        exact repeats of an earlier message of their call), cumulative since
+        the context was created (include/hd_verify.h hd_ctx_dedup_stats)."""
+        c, r = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.hd_ctx_dedup_stats(self._ctx, ctypes.byref(c), ctypes.byref(r)), "hd_ctx_dedup_stats")
+        return int(c.value), int(r.value)
 
     def fastpath_geometry(self) -> Tuple[int, int, int]:
         """(G table windows, per-key table windows, messages sharing one

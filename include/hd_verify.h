@@ -140,12 +140,22 @@ int hd_ctx_fastpath_stats(hd_ctx* ctx, uint32_t* known_keys, uint32_t* last_fall
  * fb_evict); checks = eviction checks so far (each waited for the context's
  * earlier verify calls).  Any may be NULL; synchronises the context's calls. */
 int hd_ctx_foreign_stats(hd_ctx* ctx, uint32_t* ready_slots, uint32_t* evictions, uint32_t* checks);
+/* Repeats of the known-key check (HD_VAR_DEDUP), cumulative since context
+ * creation, from device counters: checked = messages that entered the check
+ * (known key, valid type, signature in range), repeats = those of them that
+ * were exact repeats of an earlier message of their call and were served from
+ * its check.  checked - repeats is the number of checks executed.  Either may
+ * be NULL; synchronises the context's calls. */
+int hd_ctx_dedup_stats(hd_ctx* ctx, uint64_t* checked, uint64_t* repeats);
 /* Shape of the known-key check as the context runs it now (for cost models):
  * g_windows / key_windows: fixed-base windows of the G table and of the
  * per-key tables (one table point each; the first is loaded, the rest are
  * mixed additions); msgs_per_inversion: messages that share one inversion of
- * each kind in the last verify call (the split check takes 16 from 2^20 - 2^16
- * messages up, else 8; 2 for the paired kernel).
+ * each kind in the last verify call (the split check takes 16 from 2^19
+ * expected distinct checked messages up, else 8: the batch size times the
+ * share of distinct messages in the latest finished call, so with calls in
+ * flight the value can depend on which of them has finished; HD_VAR_SPLIT_K
+ * pins it; 2 for the paired kernel).
  * Host-only (no device access); any pointer may be NULL. */
 int hd_ctx_fastpath_geometry(hd_ctx* ctx, int* g_windows, int* key_windows, int* msgs_per_inversion);
 /* Device-time profile for roofline reports.  While enabled, every verify
@@ -165,8 +175,8 @@ int hd_ctx_profile(hd_ctx* ctx, int enable);
 #define HD_VAR_SUM_WAVES 1      /* k_fast_sums waves per SIMD: 2, 3 or 4 (128 VGPRs, table points loaded when
                                    used); 0 (default) 4 for batches under two rounds at 3, else 3 [HD_SUM_WAVES] */
 #define HD_VAR_SUM_PREFETCH 2   /* k_fast_sums table-point prefetch depth: 1 (default) or 2 [HD_SUM_PF] */
-#define HD_VAR_SPLIT_K 4        /* messages per inversion of the known-key check: -1 by batch size (default),
-                                   8 or 16 [HD_FAST_K] */
+#define HD_VAR_SPLIT_K 4        /* messages per inversion of the known-key check: -1 by the number of distinct
+                                   checked messages (default), 8 or 16 [HD_FAST_K] */
 #define HD_VAR_RECOVER_G 5      /* the full recovery's u1 G: 0 from the fixed-base G table (default), 1 from the
                                    GLV ladder's own 12-bit table [HD_RECOVER_GLV_G] */
 #define HD_VAR_KEY_WIDTH 7      /* per-key table windows: 0 by the table budget (default: 22 while every key's
@@ -188,10 +198,16 @@ int hd_ctx_profile(hd_ctx* ctx, int enable);
 #define HD_VAR_SLOW_LIFT 11     /* the known-key check's leftovers: 1 (default) a lift kernel first (x^3 + 7 a
                                    square, else NO_POINT), then the full recovery over the rest; 0 the full
                                    recovery over every leftover (it checks the lift itself) [HD_SLOW_LIFT] */
-/* Keys 3, 6, 9, 12, 13 and 14 (the digit pass, the paired kernel's waves, the
- * sums residency cap, the fused comparison, the lean inversions and the sums
- * chain) were measured without gain and removed in round 5: set returns
- * HD_EINVAL for them, get returns their fixed value. */
+#define HD_VAR_DEDUP 12         /* repeats in the known-key check: 1 (default) a vote whose height, round,
+                                   value, From and 65 signature bytes equal an earlier live vote's of the
+                                   same call (the Prevote / Precommit pair of one signatory and value, a
+                                   replay) is checked once and every copy gets that check's outputs; 0 no
+                                   message is ever marked a repeat (same kernels, same compaction)
+                                   [HD_DEDUP] */
+/* Keys 3, 6, 9, 13 and 14 (the digit pass, the paired kernel's waves, the
+ * sums residency cap, the lean inversions and the sums chain) were measured
+ * without gain and removed in round 5: set returns HD_EINVAL for them, get
+ * returns their fixed value. */
 #define HD_VAR__COUNT 15
 int hd_ctx_set_variant(hd_ctx* ctx, int which, int value);
 int hd_ctx_get_variant(hd_ctx* ctx, int which, int* value);
