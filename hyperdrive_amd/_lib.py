@@ -91,6 +91,20 @@ class HdTallyOut(ctypes.Structure):
     ]
 
 
+class HdDecideIn(ctypes.Structure):
+    """include/hd_verify.h hd_decide_in."""
+    _fields_ = [("f", ctypes.c_uint32), ("n_sched", ctypes.c_uint32), ("sched32", ctypes.c_void_p),
+                ("value_ok", ctypes.c_void_p)]
+
+
+class HdDecideOut(ctypes.Structure):
+    """include/hd_verify.h hd_decide_out (hd_decide / hd_decide_device_bitmap)."""
+    ROW_FIELDS = ["height", "round", "rep", "propose", "prevotes", "precommits", "trace", "pv_value", "pc_value",
+                  "pv_nil", "pv_validround", "flags", "bits"]
+    _fields_ = [("cap", ctypes.c_uint32), ("n", ctypes.c_uint32)] + [(k, ctypes.c_void_p) for k in ROW_FIELDS] + [
+        ("pclass", ctypes.c_void_p), ("dup", ctypes.c_void_p)]
+
+
 class HdTallyTicket(ctypes.Structure):
     """include/hd_verify.h hd_tally_ticket (hd_tally_device_bitmap_async / hd_tally_collect)."""
     _fields_ = [("stage", ctypes.c_void_p), ("stage_cap", ctypes.c_size_t), ("dup", ctypes.c_int),
@@ -151,6 +165,11 @@ SIGNATURES = {
     "hd_tally_ticket_release": (ctypes.c_int, [ctypes.POINTER(HdTallyTicket)]),
     "hd_process_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HdTallyOut)]),
+    "hd_decide": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                 ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut)]),
+    "hd_decide_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                               ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
+                                               ctypes.c_void_p]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

@@ -29,6 +29,10 @@
 // Non-winners compare their value with the winner's: identical -> dropped
 // silently, different -> the double vote handed to Catcher.CatchDouble*
 // (process.go:838-843, 875-880).
+//
+// hd_decide (the end of this file) runs the same passes with the propose log
+// of process.go:758-819 beside them -- a fourth claim table P keyed (h, r) --
+// and turns each round's counts into one row with the eight predicate bits.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -47,7 +51,7 @@ using namespace hd;
 static const uint32_t kEmpty = 0xFFFFFFFFu;
 
 struct TallyWork {
-    DevBuf b[15];
+    DevBuf b[21];
     void* host = nullptr;   // pinned download stage (hipHostMalloc)
     size_t host_cap = 0;
     uint32_t* scalar = nullptr;   // pinned word (a partition's candidate count)
@@ -59,15 +63,24 @@ struct TallyWork {
     bool dirty = false;
     const void* tab_p = nullptr;
     uint32_t tab_k = 0;
+    // hd_decide: the propose claim table (cleaned by k_decide_clean) and the
+    // staged row capacity
+    std::atomic<uint32_t> guess_dec{1024};
+    bool pdirty = false;
+    const void* ptab_p = nullptr;
+    uint32_t ptab_k = 0;
 };
 // T_G: the hash tables and call counters; T_C: the dense log cells; T_D /
 // T_SORTK / T_TMP: a partition's candidate compaction; T_GSLOT / T_DSLOT /
 // T_CSLOT: per-item round slot, log reference and count slot; T_BITS: the
 // first-item bitmaps and their prefixes; T_SEL: the output stage; T_NSEL: the
 // overflow rows; T_DUP: a routed batch's classification when it is scattered
-// on the device instead of staged; T_CHECK: HD_TALLY_CHECK's counters
+// on the device instead of staged; T_CHECK: HD_TALLY_CHECK's counters;
+// hd_decide: T_P the propose claim table, T_PSLOT per-item propose slot,
+// T_DSTAGE / T_DOVF its output stage and overflow rows, T_SCHED / T_VOK the
+// host form's uploaded schedule and value_ok bytes
 enum TSlot { T_G, T_D, T_C, T_GSLOT, T_DSLOT, T_NSEL, T_SEL, T_SORTK, T_SORTV, T_TMP, T_DUP, T_ROUTE, T_CHECK,
-             T_CSLOT, T_BITS };
+             T_CSLOT, T_BITS, T_P, T_PSLOT, T_DSTAGE, T_DOVF, T_SCHED, T_VOK };
 
 // table layouts (structure of arrays inside one allocation, capacity cap)
 struct GTab {   // (h, r)
@@ -1498,6 +1511,491 @@ int hd_process_batch(hd_ctx* ctx, const hd_batch* batch, uint8_t* verdict, uint8
     rc = hd_verify_uploaded(ctx, &db, verdict, recovered32, valid_bitmap);
     if (rc) return rc;
     return tally_device(ctx, &db, (const uint8_t*)ctx->bufs[BUF_VERDICT].p, nullptr, Part{0, 1}, tally, ctx->stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ decide
+// hd_decide: the tally's tables plus the propose log of process.go:758-819,
+// and one row per round with the counts and the eight predicate bits the
+// 2f+1 / f+1 rules read (include/hd_verify.h).  The launch sequence is the
+// tally's with two propose passes and a decide pass inside it, while the G /
+// C / log tables are populated:
+//
+//   k_decide_claim   every eligible propose -> its round's slot of P, a claim
+//                    table keyed (h, r): first-wins = the lowest batch index
+//                    (CAS / atomicMin, wavefront-leader probing as pass 1);
+//                    the other messages get their class (3, or 4 out of turn)
+//   k_tally_rounds, k_tally_logs, k_tally_values      unchanged
+//   k_decide_log     P's winners are the logged proposes: each takes (or
+//                    creates -- a round no vote names) its round's G slot with
+//                    its batch index, so a round's first item is its first
+//                    vote candidate or logged propose; the other eligible
+//                    proposes compare with the winner (Equal, message.go:83-89)
+//   k_tally_firsts   unchanged: the first-item bitmap and its prefixes
+//   k_decide_emit    each round's first item writes the round's row: counts
+//                    from G, the propose from P, per-value counts by lookups
+//                    in C (this round's and (h, valid_round)'s), "signer is
+//                    new" from the round's dense log cells or D.  Read-only on
+//                    the tables, so rows may read other rounds' slots
+//   k_decide_clean   every first item / winner resets its slots of G, C, D
+//                    and P: the tables are clean for the next call (tally or
+//                    decide), as after k_tally_emit
+struct DecideCols {
+    int64_t *h, *r;
+    uint32_t *rep, *propose, *prevotes, *precommits, *trace, *pv_value, *pc_value, *pv_nil, *pv_validround;
+    uint8_t *flags, *bits;
+};
+#define HD_DECIDE_ROW_BYTES 54u   // 2 x 8 + 9 x 4 + 2
+HD_HOSTONLY DecideCols decide_cols(char* base, uint32_t cap) {
+    DecideCols x;
+    x.h = reinterpret_cast<int64_t*>(base);
+    x.r = x.h + cap;
+    x.rep = reinterpret_cast<uint32_t*>(x.r + cap);
+    x.propose = x.rep + cap;
+    x.prevotes = x.propose + cap;
+    x.precommits = x.prevotes + cap;
+    x.trace = x.precommits + cap;
+    x.pv_value = x.trace + cap;
+    x.pc_value = x.pv_value + cap;
+    x.pv_nil = x.pc_value + cap;
+    x.pv_validround = x.pv_nil + cap;
+    x.flags = reinterpret_cast<uint8_t*>(x.pv_validround + cap);
+    x.bits = x.flags + cap;
+    return x;
+}
+
+struct DecideIn {
+    uint32_t f, n_sched;
+    const uint8_t* sched32;    // device
+    const uint8_t* value_ok;   // device
+};
+
+__device__ __forceinline__ bool msg_valid(const uint8_t* verdict, const uint32_t* bitmap, uint32_t i) {
+    if (verdict && verdict[i] != V_VALID) return false;
+    if (bitmap && !((bitmap[i >> 5] >> (i & 31)) & 1u)) return false;
+    return true;
+}
+
+// class of message i before the log is known: 0 eligible, 3 not a propose
+// candidate, 4 out of turn (process.go:759-781)
+__device__ __forceinline__ uint8_t propose_class(const DevBatch& b, const uint8_t* verdict, const uint32_t* bitmap,
+                                                 const DecideIn& in, uint32_t i) {
+    if (b.type[i] != T_PROPOSE || !msg_valid(verdict, bitmap, i)) return 3;
+    const int64_t h = b.height[i], r = b.round[i];
+    if (r <= -1) return 3;                         // process.go:763
+    if (!in.sched32) return 0;                     // p.scheduler == nil (770)
+    if (h <= 0) return 3;
+    const uint64_t turn = ((uint64_t)h + (uint64_t)r) % in.n_sched;   // scheduler.go:52
+    uint32_t from[8], want[8];
+    load_row32_be(from, b.from32, i);
+    load_row32_be(want, in.sched32, turn);
+    uint32_t diff = 0;
+    HD_UNROLL for (int k = 0; k < 8; k++) diff |= from[k] ^ want[k];
+    return diff ? 4 : 0;
+}
+
+__global__ void k_decide_claim(DevBatch b, const uint8_t* __restrict__ verdict, const uint32_t* __restrict__ bitmap,
+                               DecideIn in, uint32_t* __restrict__ P, uint32_t mask, uint32_t* __restrict__ pslot,
+                               uint8_t* __restrict__ pclass) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    const int lane = threadIdx.x & 63;
+    for (uint32_t base = blockIdx.x * blockDim.x; base < b.n; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        bool e = false;
+        if (i < b.n) {
+            const uint8_t cls = propose_class(b, verdict, bitmap, in, i);
+            e = cls == 0;
+            if (!e) {
+                pslot[i] = kEmpty;
+                if (pclass) pclass[i] = cls;
+            }
+        }
+        const unsigned long long act = __ballot(e);
+        if (!act) continue;
+        const int lead = __ffsll((long long)act) - 1;
+        const int64_t h = e ? b.height[i] : 0, r = e ? b.round[i] : 0;
+        const int64_t hl = shfl64(h, lead), rl = shfl64(r, lead);   // every lane takes part in the shuffles
+        const bool follower = e && lane != lead && hl == h && rl == r;
+        uint32_t s = kEmpty;
+        if (e && !follower) {
+            bool created;
+            s = probe(P, mask, hash_hr(h, r), i, [&](uint32_t o) { return b.height[o] == h && b.round[o] == r; },
+                      created);
+        }
+        const uint32_t sl = (uint32_t)__shfl((int)s, lead, 64);
+        if (e) pslot[i] = follower ? sl : s;
+    }
+}
+
+__global__ void k_decide_log(DevBatch b, const uint32_t* __restrict__ P, const uint32_t* __restrict__ pslot, GTab G,
+                             uint32_t mask, uint32_t* __restrict__ gslot, uint32_t* __restrict__ cslot,
+                             uint32_t* __restrict__ ref, uint8_t* __restrict__ pclass) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < b.n; i += stride) {
+        const uint32_t ps = pslot[i];
+        if (ps == kEmpty) continue;
+        const uint32_t w = P[ps];
+        if (w == i) {   // logged (process.go:804, 811): the round's row may start here
+            const int64_t h = b.height[i], r = b.round[i];
+            bool created;
+            gslot[i] = probe(G.claim, mask, hash_hr(h, r), i,
+                             [&](uint32_t o) { return b.height[o] == h && b.round[o] == r; }, created);
+            cslot[i] = kEmpty;   // no count group, no log cell
+            ref[i] = 0;
+            if (pclass) pclass[i] = 0;
+        } else if (pclass) {     // process.go:788-795
+            const bool same_vr = !b.valid_round || b.valid_round[w] == b.valid_round[i];
+            const bool equal = same_vr && eq32(b.value32 + 32 * (size_t)w, b.value32 + 32 * (size_t)i) &&
+                               eq32(b.from32 + 32 * (size_t)w, b.from32 + 32 * (size_t)i);
+            pclass[i] = equal ? 1 : 2;
+        }
+    }
+}
+
+// first-wins votes of (G slot g, type t) for the value (v0, v1): C.n of the
+// key's slot, 0 when no vote carries it (hash_count's hash, from registers)
+__device__ __forceinline__ uint32_t count_of(const CTab& C, uint32_t mask, const DevBatch& b,
+                                             const uint32_t* gslot, uint32_t g, uint8_t t, uint4 v0, uint4 v1) {
+    const uint64_t hv = ((uint64_t)v0.y << 32 | v0.x) ^ ((uint64_t)v0.w << 32 | v0.z);
+    const uint32_t c = find(C.claim, mask, mix64(hv ^ ((uint64_t)g << 1 | (t & 1u))), [&](uint32_t o) {
+        if (gslot[o] != g || b.type[o] != t) return false;
+        const uint4* p = reinterpret_cast<const uint4*>(b.value32 + 32 * (size_t)o);
+        const uint4 a = p[0], d = p[1];
+        return ((a.x ^ v0.x) | (a.y ^ v0.y) | (a.z ^ v0.z) | (a.w ^ v0.w) | (d.x ^ v1.x) | (d.y ^ v1.y) |
+                (d.z ^ v1.z) | (d.w ^ v1.w)) == 0;
+    });
+    return c == kEmpty ? 0u : C.n[c];
+}
+
+template <uint32_t IPB>
+__global__ __launch_bounds__(256) void k_decide_emit(DevBatch b, uint32_t m, DecideIn in,
+                                                     const uint32_t* __restrict__ gslot, GTab G, CTab C,
+                                                     const uint32_t* __restrict__ D, const uint32_t* __restrict__ P,
+                                                     const uint32_t* __restrict__ Dd, AdmIndex ix, uint32_t S,
+                                                     uint32_t nd, uint32_t mask, const uint32_t* __restrict__ Bg,
+                                                     const uint32_t* __restrict__ pre_g,
+                                                     const uint32_t* __restrict__ blk, DecideCols st, uint32_t H,
+                                                     DecideCols ov, uint32_t* stage_hdr) {
+    const uint32_t nb = gridDim.x;
+    __shared__ uint32_t part[4];
+    uint32_t sg = 0;
+    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += 256) sg += blk[k];
+    for (int d = 32; d > 0; d >>= 1) sg += (uint32_t)__shfl_xor((int)sg, d, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sg;
+    __syncthreads();
+    const uint32_t og = part[0] + part[1] + part[2] + part[3];
+    if (threadIdx.x == 0 && blockIdx.x == nb - 1) stage_hdr[0] = og + blk[nb - 1];   // rows
+    const uint64_t q2 = 2ull * in.f + 1ull, q1 = (uint64_t)in.f + 1ull;
+    const uint32_t lo = blockIdx.x * IPB;
+    for (uint32_t k = 0; k < IPB / 256; k++) {
+        const uint32_t q = lo + k * 256 + threadIdx.x;
+        if (q >= m) break;
+        const uint32_t g = gslot[q];
+        if (g == kEmpty) continue;
+        const uint32_t w = q >> 5, gw = Bg[w];
+        if (!((gw >> (q & 31)) & 1u)) continue;
+        const uint32_t pos = og + pre_g[w] + (uint32_t)__popc(gw & ((1u << (q & 31)) - 1u));
+        const int64_t h = b.height[q], r = b.round[q];
+        const uint32_t np = G.nprev[g], nc = G.nprec[g], any = np + nc - G.nboth[g];
+        const uint4 zero = make_uint4(0, 0, 0, 0);
+        const uint32_t ps = find(P, mask, hash_hr(h, r), [&](uint32_t o) { return b.height[o] == h && b.round[o] == r; });
+        const uint32_t p = ps == kEmpty ? kEmpty : P[ps];
+        uint32_t pv_value = 0, pc_value = 0, pv_vr = 0, flags = 0;
+        bool valid = false, has_vr = false;
+        if (p != kEmpty) {
+            const uint4* vp = reinterpret_cast<const uint4*>(b.value32 + 32 * (size_t)p);
+            const uint4 v0 = vp[0], v1 = vp[1];
+            const bool nil = (v0.x | v0.y | v0.z | v0.w | v1.x | v1.y | v1.z | v1.w) == 0;
+            valid = !nil && (!in.value_ok || in.value_ok[p] != 0);   // process.go:803
+            pv_value = count_of(C, mask, b, gslot, g, T_PREVOTE, v0, v1);
+            pc_value = count_of(C, mask, b, gslot, g, T_PRECOMMIT, v0, v1);
+            const int64_t vr = b.valid_round ? b.valid_round[p] : -1;
+            has_vr = vr > -1;
+            if (has_vr) {   // process.go:486-491
+                const uint32_t g2 = vr == r ? g : find(G.claim, mask, hash_hr(h, vr), [&](uint32_t o) {
+                    return b.height[o] == h && b.round[o] == vr;
+                });
+                if (g2 != kEmpty) pv_vr = count_of(C, mask, b, gslot, g2, T_PREVOTE, v0, v1);
+            }
+            bool fresh = false;
+            if (valid) {    // process.go:813-816: is From already in TraceLogs[r]?
+                bool seen = false;
+                if (np + nc) {
+                    const uint32_t rid = G.gid[g];
+                    int32_t signer = -1;
+                    if (rid < nd) {
+                        uint32_t from_be[8];
+                        load_row32_be(from_be, b.from32, p);
+                        signer = adm_index_find(ix, from_be);
+                    }
+                    if (signer >= 0) {   // the dense cells of (round, prevote | precommit, signer)
+                        const uint32_t cell = rid * 2u * S + (uint32_t)signer;
+                        seen = Dd[cell] != kEmpty || Dd[cell + S] != kEmpty;
+                    } else {
+                        const uint8_t* from = b.from32 + 32 * (size_t)p;
+                        const uint64_t hhr = hash_hr(h, r);
+                        for (uint32_t t = T_PREVOTE; t <= T_PRECOMMIT && !seen; t++)
+                            seen = find(D, mask, hash_log(hhr, from, t), [&](uint32_t c) {
+                                       return b.type[c] == t && b.height[c] == h && b.round[c] == r &&
+                                              eq32(b.from32 + 32 * (size_t)c, from);
+                                   }) != kEmpty;
+                    }
+                }
+                fresh = !seen;
+            }
+            flags = 1u | (valid ? 2u : 0u) | (fresh ? 4u : 0u);
+        }
+        const uint32_t pv_nil = count_of(C, mask, b, gslot, g, T_PREVOTE, zero, zero);
+        const uint32_t trace = any + ((flags >> 2) & 1u);
+        uint32_t bits = 0;
+        bits |= np >= q2 ? 1u : 0u;                        // timeout_prevote
+        bits |= pv_nil >= q2 ? 2u : 0u;                    // precommit_nil
+        bits |= nc >= q2 ? 4u : 0u;                        // timeout_precommit_reached
+        bits |= nc == q2 ? 8u : 0u;                        // timeout_precommit_exact
+        bits |= trace >= q1 ? 16u : 0u;                    // skip
+        bits |= valid && pv_value >= q2 ? 32u : 0u;        // precommit_value
+        bits |= valid && pc_value >= q2 ? 64u : 0u;        // commit
+        bits |= has_vr && pv_vr >= q2 ? 128u : 0u;         // prevote_validround
+        const DecideCols& x = pos < H ? st : ov;
+        const uint32_t j = pos < H ? pos : pos - H;
+        x.h[j] = h;
+        x.r[j] = r;
+        x.rep[j] = q;
+        x.propose[j] = p;
+        x.prevotes[j] = np;
+        x.precommits[j] = nc;
+        x.trace[j] = trace;
+        x.pv_value[j] = pv_value;
+        x.pc_value[j] = pc_value;
+        x.pv_nil[j] = pv_nil;
+        x.pv_validround[j] = pv_vr;
+        x.flags[j] = (uint8_t)flags;
+        x.bits[j] = (uint8_t)bits;
+    }
+}
+
+// after k_decide_emit: every table slot back to empty / zero by the item that
+// owns it (a round's first item, a count group's and a hashed log's winner,
+// a logged propose), and the round numbering restarts
+__global__ void k_decide_clean(uint32_t m, const uint32_t* __restrict__ gslot, const uint32_t* __restrict__ cslot,
+                               const uint32_t* __restrict__ ref, const uint32_t* __restrict__ pslot, GTab G, CTab C,
+                               uint32_t* __restrict__ D, uint32_t* __restrict__ P, const uint32_t* __restrict__ Bg,
+                               TallyCtr* ctr) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) ctr->n_rounds = 0;
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < m; q += stride) {
+        const uint32_t ps = pslot[q];
+        if (ps != kEmpty && P[ps] == q) P[ps] = kEmpty;
+        const uint32_t g = gslot[q];
+        if (g == kEmpty) continue;
+        if ((Bg[q >> 5] >> (q & 31)) & 1u) {
+            G.claim[g] = kEmpty;
+            G.nprev[g] = G.nprec[g] = G.nboth[g] = 0;
+        }
+        const uint32_t c = cslot[q];
+        if (c != kEmpty && C.claim[c] == q) {
+            C.claim[c] = kEmpty;
+            C.n[c] = 0;
+        }
+        const uint32_t rf = ref[q];
+        if ((rf & HD_REF_HASHED) && D[rf & ~HD_REF_HASHED] == q) D[rf & ~HD_REF_HASHED] = kEmpty;
+    }
+}
+
+static size_t decide_pad(size_t n) { return (n + 63) & ~(size_t)63; }
+
+static bool decide_out_ok(const hd_decide_out* o) {
+    return o && o->height && o->round && o->rep && o->propose && o->prevotes && o->precommits && o->trace &&
+           o->pv_value && o->pc_value && o->pv_nil && o->pv_validround && o->flags && o->bits;
+}
+
+static void decide_unpack(const DecideCols& x, uint32_t rows, uint32_t at, hd_decide_out* out) {
+    if (!rows) return;
+    memcpy(out->height + at, x.h, 8 * (size_t)rows);
+    memcpy(out->round + at, x.r, 8 * (size_t)rows);
+    uint32_t* const dst[] = {out->rep, out->propose, out->prevotes, out->precommits, out->trace,
+                             out->pv_value, out->pc_value, out->pv_nil, out->pv_validround};
+    const uint32_t* const src[] = {x.rep, x.propose, x.prevotes, x.precommits, x.trace,
+                                   x.pv_value, x.pc_value, x.pv_nil, x.pv_validround};
+    for (int k = 0; k < 9; k++) memcpy(dst[k] + at, src[k], 4 * (size_t)rows);
+    memcpy(out->flags + at, x.flags, rows);
+    memcpy(out->bits + at, x.bits, rows);
+}
+
+// Whole batch only (items = batch indices).  One download of the stage
+// [rows | dup (n bytes, when asked) | pclass (n bytes, when asked) | rows at
+// capacity H]; rows past H come from the overflow columns by a second round
+// of copies.
+static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap,
+                         DecideIn in, hd_decide_out* out, hipStream_t s) {
+    const uint32_t n = hb->n, m = n;
+    if (!ctx->tally) ctx->tally = new TallyWork();
+    TallyWork* tw = ctx->tally;
+    DevBatch b{n, hb->type, hb->height, hb->round, hb->valid_round, hb->value32, hb->from32, nullptr};
+    static const uint32_t bpc = getenv("HD_TALLY_BPC") ? (uint32_t)std::max(1, atoi(getenv("HD_TALLY_BPC"))) : 16u;
+    int rc = 0;
+    const uint32_t H = tw->guess_dec;
+    const size_t dup_off = 64, pc_off = dup_off + (out->dup ? decide_pad(n) : 0),
+                 rows_off = pc_off + (out->pclass ? decide_pad(n) : 0);
+    const size_t total = rows_off + HD_DECIDE_ROW_BYTES * (size_t)H + 64;
+    char* st = (char*)tbuf(ctx, T_DSTAGE, total, &rc);
+    if (rc) return rc;
+    uint8_t* d_dup = out->dup ? (uint8_t*)(st + dup_off) : nullptr;
+    uint8_t* d_pclass = out->pclass ? (uint8_t*)(st + pc_off) : nullptr;
+    const uint32_t grid = std::min<uint32_t>(nblk(m), (uint32_t)ctx->n_cu * bpc);
+    uint32_t cap = 1024;
+    while (cap < 2 * m) cap <<= 1;
+    const uint32_t mask = cap - 1;
+    const uint32_t ipb = tally_ipb(m, (uint32_t)ctx->n_cu);
+    const uint32_t nbo = (m + ipb - 1) / ipb;
+    const size_t nw = (size_t)nbo * (ipb / 32);
+    const size_t K = cap;
+    // the tally's tables, scratch and dense cells, laid out exactly as tally_device does
+    char* tb = (char*)tbuf(ctx, T_G, 4 * 8 * K + sizeof(TallyCtr), &rc);
+    uint32_t* gslot = (uint32_t*)tbuf(ctx, T_GSLOT, 4 * (size_t)m, &rc);
+    uint32_t* ref = (uint32_t*)tbuf(ctx, T_DSLOT, 4 * (size_t)m, &rc);
+    uint32_t* cslot = (uint32_t*)tbuf(ctx, T_CSLOT, 4 * (size_t)m, &rc);
+    uint32_t* bits = (uint32_t*)tbuf(ctx, T_BITS, 4 * (4 * nw + 2 * (size_t)nbo), &rc);
+    uint32_t* P = (uint32_t*)tbuf(ctx, T_P, 4 * K, &rc);
+    uint32_t* pslot = (uint32_t*)tbuf(ctx, T_PSLOT, 4 * (size_t)m, &rc);
+    char* ovf = (char*)tbuf(ctx, T_DOVF, HD_DECIDE_ROW_BYTES * (size_t)m + 64, &rc);
+    const uint32_t S = ctx->n_adm;
+    const size_t dcap = S > 0 ? std::min<size_t>(HD_TALLY_DENSE_MAX, (size_t)m * 2 * S) : 0;
+    const uint32_t nd = S > 0 ? (uint32_t)(dcap / (2 * (size_t)S)) : 0u;
+    uint32_t* Dd = dcap ? (uint32_t*)tbuf(ctx, T_C, 4 * dcap, &rc) : nullptr;
+    if (rc) return rc;
+    uint32_t* tabs = (uint32_t*)tb;
+    GTab G{tabs, tabs + 3 * K, tabs + 4 * K, tabs + 5 * K, tabs + 7 * K};
+    CTab C{tabs + K, tabs + 6 * K};
+    uint32_t* d = tabs + 2 * K;
+    TallyCtr* ctr = reinterpret_cast<TallyCtr*>(tb + 4 * 8 * K);
+    if (tw->dirty || tw->tab_p != tb || tw->tab_k != cap) {
+        TCHK(hipMemsetAsync(tabs, 0xFF, 4 * 3 * K, s), "clear claims");
+        TCHK(hipMemsetAsync(tabs + 3 * K, 0, 4 * 4 * K, s), "clear counters");
+        TCHK(hipMemsetAsync(ctr, 0, sizeof(TallyCtr), s), "clear call counters");
+        tw->tab_p = tb;
+        tw->tab_k = cap;
+    }
+    if (tw->pdirty || tw->ptab_p != P || tw->ptab_k != cap) {
+        TCHK(hipMemsetAsync(P, 0xFF, 4 * K, s), "clear propose claims");
+        tw->ptab_p = P;
+        tw->ptab_k = cap;
+    }
+    tw->dirty = tw->pdirty = true;   // until every launch below is queued
+    const AdmIndex ix = hd_adm_index(ctx);
+    k_decide_claim<<<grid, 256, 0, s>>>(b, d_verdict, d_bitmap, in, P, mask, pslot, d_pclass);
+    k_tally_rounds<<<grid, 256, 0, s>>>(b, nullptr, m, d_verdict, d_bitmap, Part{0, 1}, G, mask, gslot, d_dup, ctr, Dd,
+                                        2 * S, nd);
+    k_tally_logs<<<grid, 256, 0, s>>>(b, nullptr, m, gslot, G.gid, ix, S, Dd, nd, d, mask, ref);
+    k_tally_values<<<grid, 256, 0, s>>>(b, nullptr, m, Dd, S, d, G, C, mask, gslot, ref, cslot, d_dup);
+    k_decide_log<<<grid, 256, 0, s>>>(b, P, pslot, G, mask, gslot, cslot, ref, d_pclass);
+    TCHK(hipGetLastError(), "decide kernels");
+    uint32_t *Bg = bits, *Bc = bits + nw, *pre_g = bits + 2 * nw, *pre_c = bits + 3 * nw, *blk = bits + 4 * nw;
+    const DecideCols sc = decide_cols(st + rows_off, H), oc = decide_cols(ovf, m);
+    switch (ipb) {
+#define HD_DECIDE_ORDER(IPB)                                                                                     \
+    case IPB:                                                                                                    \
+        k_tally_firsts<IPB><<<nbo, 256, 0, s>>>(m, gslot, cslot, G.claim, C.claim, Bg, Bc, pre_g, pre_c, blk);    \
+        k_decide_emit<IPB><<<nbo, 256, 0, s>>>(b, m, in, gslot, G, C, d, P, Dd, ix, S, nd, mask, Bg, pre_g, blk,  \
+                                               sc, H, oc, (uint32_t*)st);                                        \
+        break;
+        HD_DECIDE_ORDER(256u)
+        HD_DECIDE_ORDER(512u)
+        HD_DECIDE_ORDER(1024u)
+        HD_DECIDE_ORDER(2048u)
+#undef HD_DECIDE_ORDER
+    }
+    k_decide_clean<<<grid, 256, 0, s>>>(m, gslot, cslot, ref, pslot, G, C, d, P, Bg, ctr);
+    TCHK(hipGetLastError(), "decide order kernels");
+    tw->dirty = tw->pdirty = false;
+    if (tw->host_cap < total) {
+        if (tw->host) (void)hipHostFree(tw->host);
+        tw->host = nullptr;
+        tw->host_cap = 0;
+        TCHK(hipHostMalloc(&tw->host, total + (total >> 2), hipHostMallocDefault), "decide host stage");
+        tw->host_cap = total + (total >> 2);
+    }
+    TCHK(hipMemcpyAsync(tw->host, st, total, hipMemcpyDeviceToHost, s), "decide download");
+    TCHK(hipStreamSynchronize(s), "decide sync");
+    const char* hs = (const char*)tw->host;
+    const uint32_t rows = reinterpret_cast<const uint32_t*>(hs)[0];
+    out->n = rows;
+    tw->guess_dec = std::max<uint32_t>(1024u, rows + rows / 4);
+    if (rows > out->cap) return HD_ECAP;
+    if (out->dup) memcpy(out->dup, hs + dup_off, n);
+    if (out->pclass) memcpy(out->pclass, hs + pc_off, n);
+    decide_unpack(decide_cols(const_cast<char*>(hs) + rows_off, H), std::min(rows, H), 0, out);
+    if (rows > H) {   // more rounds than staged: the overflow columns, straight into out
+        const uint32_t e = rows - H;
+        struct Piece {
+            void* dst;
+            const void* src;
+            size_t sz;
+        } pieces[] = {
+            {out->height + H, oc.h, 8 * (size_t)e},           {out->round + H, oc.r, 8 * (size_t)e},
+            {out->rep + H, oc.rep, 4 * (size_t)e},            {out->propose + H, oc.propose, 4 * (size_t)e},
+            {out->prevotes + H, oc.prevotes, 4 * (size_t)e},  {out->precommits + H, oc.precommits, 4 * (size_t)e},
+            {out->trace + H, oc.trace, 4 * (size_t)e},        {out->pv_value + H, oc.pv_value, 4 * (size_t)e},
+            {out->pc_value + H, oc.pc_value, 4 * (size_t)e},  {out->pv_nil + H, oc.pv_nil, 4 * (size_t)e},
+            {out->pv_validround + H, oc.pv_validround, 4 * (size_t)e},
+            {out->flags + H, oc.flags, (size_t)e},            {out->bits + H, oc.bits, (size_t)e},
+        };
+        for (const Piece& p : pieces) TCHK(hipMemcpyAsync(p.dst, p.src, p.sz, hipMemcpyDeviceToHost, s), "decide overflow");
+        TCHK(hipStreamSynchronize(s), "decide overflow sync");
+    }
+    return HD_OK;
+}
+
+extern "C" {
+
+int hd_decide(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in, hd_decide_out* out) {
+    if (!ctx || !batch || !verdict || !in || !decide_out_ok(out)) return HD_EINVAL;
+    if (!batch->type || !batch->height || !batch->round || !batch->value32 || !batch->from32) return HD_EINVAL;
+    if (in->sched32 && in->n_sched == 0) return HD_EINVAL;
+    out->n = 0;
+    const uint32_t n = batch->n;
+    if (n == 0) return HD_OK;
+    (void)hipSetDevice(ctx->device);
+    if (!ctx->tally) ctx->tally = new TallyWork();
+    hd_batch hb = *batch;
+    hb.sig65 = nullptr;  // not needed
+    hd_batch db;
+    int rc = hd_upload_batch(ctx, &hb, &db);
+    if (rc) return rc;
+    rc = hd_dev_grow(ctx, &ctx->bufs[BUF_VERDICT].p, &ctx->bufs[BUF_VERDICT].cap, n);
+    if (rc) return rc;
+    uint8_t* d_v = (uint8_t*)ctx->bufs[BUF_VERDICT].p;
+    TCHK(hipMemcpyAsync(d_v, verdict, n, hipMemcpyHostToDevice, ctx->stream), "verdict upload");
+    DecideIn di{in->f, in->n_sched, nullptr, nullptr};
+    if (in->sched32) {
+        uint8_t* p = (uint8_t*)tbuf(ctx, T_SCHED, 32 * (size_t)in->n_sched, &rc);
+        if (rc) return rc;
+        TCHK(hipMemcpyAsync(p, in->sched32, 32 * (size_t)in->n_sched, hipMemcpyHostToDevice, ctx->stream),
+             "schedule upload");
+        di.sched32 = p;
+    }
+    if (in->value_ok) {
+        uint8_t* p = (uint8_t*)tbuf(ctx, T_VOK, n, &rc);
+        if (rc) return rc;
+        TCHK(hipMemcpyAsync(p, in->value_ok, n, hipMemcpyHostToDevice, ctx->stream), "value_ok upload");
+        di.value_ok = p;
+    }
+    return decide_device(ctx, &db, d_v, nullptr, di, out, ctx->stream);
+}
+
+int hd_decide_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                            const hd_decide_in* in, hd_decide_out* out, void* stream) {
+    if (!ctx || !dbatch || !in || !decide_out_ok(out)) return HD_EINVAL;
+    if (dbatch->n && (!d_valid_bitmap || !dbatch->type || !dbatch->height || !dbatch->round || !dbatch->value32 ||
+                      !dbatch->from32))
+        return HD_EINVAL;
+    if (in->sched32 && in->n_sched == 0) return HD_EINVAL;
+    out->n = 0;
+    if (dbatch->n == 0) return HD_OK;
+    (void)hipSetDevice(ctx->device);
+    return decide_device(ctx, dbatch, nullptr, d_valid_bitmap, DecideIn{in->f, in->n_sched, in->sched32, in->value_ok},
+                         out, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 }  // extern "C"

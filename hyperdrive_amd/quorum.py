@@ -4,7 +4,14 @@ The GPU tally (hd_tally) produces, per (height, round), the sizes of the
 first-wins vote logs and the per-value counts; these functions apply the exact
 comparisons of the reference's rules to them.  The automaton's step / once-flag
 gating (process.go's ``CurrentStep`` checks and ``OnceFlag``) is sequential
-control flow and stays with the caller.
+control flow and stays with the caller.  So does the guard of process.go:481
+(``propose.ValidRound >= CurrentRound`` returns): ``prevote_validround`` is
+computed for any ``propose_valid_round > -1``, the propose's own round and
+later ones included, and the caller applies ``valid_round < CurrentRound``.
+
+``Verifier.decide`` (hd_decide) evaluates the same eight predicates on the
+device for every round of a batch, with the propose taken from the batch's own
+propose log (process.go:758-819); its ``decisions`` are these dicts.
 """
 from __future__ import annotations
 

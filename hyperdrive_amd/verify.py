@@ -170,6 +170,49 @@ class TallyResult:
     dup: np.ndarray           # uint8[n]: 0 logged, 1 identical dup, 2 double vote, 3 not a candidate
 
 
+DECISION_KEYS = ("timeout_prevote", "precommit_nil", "timeout_precommit_reached", "timeout_precommit_exact", "skip",
+                 "precommit_value", "commit", "prevote_validround")   # bit order of hd_decide_out.bits
+NO_PROPOSE = 0xFFFFFFFF
+
+
+@dataclass
+class DecideResult:
+    """One row per (h, r) of a batch (hd_decide_out): the log lengths, the
+    logged propose, the counts for its value and the eight predicate bits,
+    computed on the device.  Rows are in the batch order of each round's first
+    vote candidate or logged propose."""
+    height: np.ndarray         # int64[rows]
+    round: np.ndarray          # int64[rows]
+    rep: np.ndarray            # uint32[rows]
+    propose: np.ndarray        # uint32[rows], NO_PROPOSE without a logged propose
+    prevotes: np.ndarray
+    precommits: np.ndarray
+    trace: np.ndarray
+    pv_value: np.ndarray
+    pc_value: np.ndarray
+    pv_nil: np.ndarray
+    pv_validround: np.ndarray
+    flags: np.ndarray          # uint8[rows]: 1 propose logged, 2 it is valid, 4 its signer was new to the trace
+    bits: np.ndarray           # uint8[rows]: DECISION_KEYS, bit k = key k
+    pclass: np.ndarray         # uint8[n]: 0 logged, 1 equal copy, 2 double propose, 3 no candidate, 4 out of turn
+    dup: np.ndarray            # uint8[n]: as TallyResult.dup
+
+    def __len__(self) -> int:
+        return len(self.height)
+
+    @property
+    def decisions(self) -> Dict[Tuple[int, int], Dict[str, bool]]:
+        """{(h, r): the dict quorum.decide returns}."""
+        return {(int(h), int(r)): {k: bool((int(b) >> j) & 1) for j, k in enumerate(DECISION_KEYS)}
+                for h, r, b in zip(self.height, self.round, self.bits)}
+
+    @property
+    def proposes(self) -> Dict[Tuple[int, int], int]:
+        """{(h, r): batch index of the logged propose}."""
+        return {(int(h), int(r)): int(p) for h, r, p in zip(self.height, self.round, self.propose)
+                if int(p) != NO_PROPOSE}
+
+
 class Verifier:
     """One context per caller thread (the reference's Process is
     single-goroutine, process/process.go:100-101)."""
@@ -407,6 +450,81 @@ class Verifier:
         self._check(self._lib.hd_process_batch(self._ctx, ctypes.byref(cb), _ptr(verdict), _ptr(rec), _ptr(bitmap),
                                                ctypes.byref(t)), "hd_process_batch")
         return VerifyResult(verdict, rec, bitmap), self._tally_result(batch, t, a)
+
+    # ---- decide ------------------------------------------------------
+    @staticmethod
+    def _decide_struct(n: int, cap: Optional[int] = None):
+        from ._lib import HdDecideOut
+        cap = n if cap is None else cap
+        dt = {"height": np.int64, "round": np.int64, "flags": np.uint8, "bits": np.uint8}
+        arrs = {k: np.zeros(max(cap, 1), dt.get(k, np.uint32)) for k in HdDecideOut.ROW_FIELDS}
+        arrs["pclass"] = np.zeros(max(n, 1), np.uint8)
+        arrs["dup"] = np.zeros(max(n, 1), np.uint8)
+        o = HdDecideOut()
+        o.cap = cap
+        for k, a in arrs.items():
+            setattr(o, k, _ptr(a))
+        return o, arrs
+
+    @staticmethod
+    def _decide_result(n: int, o, a) -> DecideResult:
+        rows = {k: a[k][: o.n].copy() for k in type(o).ROW_FIELDS}
+        return DecideResult(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), **rows)
+
+    def decide(self, batch: Batch, verdict: np.ndarray, f: int, schedule=None, value_ok=None) -> DecideResult:
+        """hd_decide: the vote logs of :meth:`tally`, the propose log of
+        process.go:758-819 and every round's eight predicates, on the device.
+        schedule: the round-robin order of signatories (rows of 32 bytes) or
+        None for no turn check; value_ok: one byte per message standing in for
+        validator.Valid on a propose's value (None: every non-nil value is
+        valid)."""
+        from ._lib import HdDecideIn
+        n = len(batch)
+        verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
+        if len(verdict) != n:
+            raise ValueError("verdict length mismatch")
+        sched = _as_rows(schedule, 32) if schedule is not None else None
+        if sched is not None and len(sched) == 0:
+            raise ValueError("an empty schedule (pass None for no turn check)")
+        vok = np.ascontiguousarray(value_ok, dtype=np.uint8) if value_ok is not None else None
+        if vok is not None and len(vok) != n:
+            raise ValueError("value_ok length mismatch")
+        o, a = self._decide_struct(n)
+        cin = HdDecideIn(int(f), len(sched) if sched is not None else 0, _ptr(sched), _ptr(vok))
+        cb = batch.c_struct()
+        self._check(self._lib.hd_decide(self._ctx, ctypes.byref(cb), _ptr(verdict), ctypes.byref(cin),
+                                        ctypes.byref(o)), "hd_decide")
+        return self._decide_result(n, o, a)
+
+    def decide_device(self, dbatch: HdBatch, d_bitmap: int, f: int, schedule=None, value_ok=None,
+                      stream: Optional[int] = None) -> DecideResult:
+        """hd_decide_device_bitmap over a device batch and the valid bitmap of
+        verify_batch_device.  schedule / value_ok: torch tensors on the device
+        (uint8 [n_sched, 32] / [n]), or host arrays, which are uploaded first."""
+        import torch
+        from ._lib import HdDecideIn
+        n = dbatch.n
+
+        def dev(x, width):
+            if x is None or isinstance(x, torch.Tensor):
+                return x
+            arr = _as_rows(x, width) if width > 1 else np.ascontiguousarray(x, dtype=np.uint8)
+            t = torch.from_numpy(arr).cuda()
+            torch.cuda.current_stream().synchronize()
+            return t
+
+        sched, vok = dev(schedule, 32), dev(value_ok, 1)
+        if sched is not None and sched.numel() == 0:
+            raise ValueError("an empty schedule (pass None for no turn check)")
+        if vok is not None and vok.numel() != n:
+            raise ValueError("value_ok length mismatch")
+        o, a = self._decide_struct(n)
+        cin = HdDecideIn(int(f), sched.numel() // 32 if sched is not None else 0,
+                         sched.data_ptr() if sched is not None else None,
+                         vok.data_ptr() if vok is not None else None)
+        self._check(self._lib.hd_decide_device_bitmap(self._ctx, ctypes.byref(dbatch), d_bitmap, ctypes.byref(cin),
+                                                      ctypes.byref(o), stream), "hd_decide_device_bitmap")
+        return self._decide_result(n, o, a)
 
     # ---- synthetic workload ------------------------------------------
     def gen_keys(self, S: int) -> Tuple[np.ndarray, np.ndarray]:

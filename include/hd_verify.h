@@ -24,6 +24,9 @@
  *                       and the counting loops of the 2f+1 / f+1 rules
  *                       (process.go:486-494, 534, 574-582, 626-632, 658,
  *                       696-702, 751), for every (height, round) of a batch.
+ *   hd_decide           the same plus the propose log (insertPropose,
+ *                       process.go:758-819) and the rules' count predicates
+ *                       themselves, one row per (height, round).
  *
  * Ownership: all host buffers are caller-owned; the library copies what it
  * needs and keeps no pointer after a call returns.  Device buffers passed to
@@ -407,6 +410,87 @@ uint32_t hd_tally_partition_of(int64_t height, int64_t round, uint32_t nparts);
 /* verify + tally with one upload of the batch */
 int hd_process_batch(hd_ctx* ctx, const hd_batch* batch, uint8_t* verdict, uint8_t* recovered32,
                      uint32_t* valid_bitmap, hd_tally_out* tally);
+
+/* ---- decide: every round's quorum rules, proposes included ---------------
+ * The tally above plus the propose log of process.go:758-819 and the count
+ * predicates that read it, one row per (height, round), all on the device.
+ *
+ * Vote logs: exactly hd_tally's (first-wins per (h, r, type, From)).
+ *
+ * Propose log per (h, r).  A propose is ELIGIBLE when it is VALID, its round
+ * is > -1 (process.go:763) and, with a schedule, its height is > 0 and its
+ * From is sched32[(uint64(h) + uint64(r)) % n_sched] (scheduler.go:52;
+ * process.go:770-781).  Without a schedule (sched32 NULL) there is no turn
+ * check.  Among a round's eligible proposes the lowest batch index is LOGGED
+ * (process.go:788-795, 804, 811).  pclass[i]:
+ *   0  logged
+ *   1  eligible and Equal to the logged one (message.go:83-89: height, round,
+ *      valid_round, value, From -- not the signature): dropped silently
+ *   2  eligible and not Equal: Catcher.CatchDoublePropose(this, logged)
+ *   3  not a propose candidate (not a propose, not VALID, round <= -1, or
+ *      height <= 0 with a schedule)
+ *   4  VALID propose out of turn: Catcher.CatchOutOfTurnPropose
+ * The logged propose is valid (process.go:803) when its value is not NilValue
+ * and value_ok[i] is nonzero (value_ok stands in for validator.Valid, run by
+ * the caller before the call; NULL: every non-nil value is valid).  A valid
+ * logged propose adds its From to the round's trace (813-816); an invalid one
+ * is logged but not traced.
+ *
+ * One row per (h, r) that has a vote candidate or a logged propose, in the
+ * batch order of the round's first such message.  bits (thresholds from f):
+ *   bit 0 timeout_prevote            prevotes >= 2f+1                  (534)
+ *   bit 1 precommit_nil              pv_nil >= 2f+1                (626-632)
+ *   bit 2 timeout_precommit_reached  precommits >= 2f+1                (658)
+ *   bit 3 timeout_precommit_exact    precommits == 2f+1           (310, 658)
+ *   bit 4 skip                       trace >= f+1                      (751)
+ *   bit 5 precommit_value            valid propose, pv_value >= 2f+1 (574-582)
+ *   bit 6 commit                     valid propose, pc_value >= 2f+1 (696-702)
+ *   bit 7 prevote_validround         propose with valid_round > -1,
+ *                                    pv_validround >= 2f+1         (486-494)
+ * The bits are count predicates over the batch's final logs.  The automaton's
+ * step and once-flag gating stays with the caller, and so does the
+ * `valid_round < CurrentRound` guard of process.go:481: bit 7 is computed for
+ * any valid_round > -1, the propose's own round and later ones included. */
+typedef struct {
+    uint32_t f;               /* the thresholds are 2f+1 and f+1 */
+    uint32_t n_sched;         /* entries of sched32 */
+    const uint8_t* sched32;   /* n_sched x 32 bytes (the round-robin order), or NULL */
+    const uint8_t* value_ok;  /* n bytes, or NULL */
+} hd_decide_in;
+
+typedef struct {
+    uint32_t cap;             /* capacity of the row arrays */
+    uint32_t n;               /* rows (the need, when HD_ECAP) */
+    int64_t* height;
+    int64_t* round;
+    uint32_t* rep;            /* batch index of the round's first vote candidate or logged propose */
+    uint32_t* propose;        /* batch index of the logged propose, or 0xFFFFFFFF */
+    uint32_t* prevotes;       /* len(PrevoteLogs[r])   */
+    uint32_t* precommits;     /* len(PrecommitLogs[r]) */
+    uint32_t* trace;          /* len(TraceLogs[r]): distinct vote signers, +1 for a valid logged
+                                 propose whose From is not among them */
+    uint32_t* pv_value;       /* first-wins prevotes / precommits of this round for the logged */
+    uint32_t* pc_value;       /*   propose's value (0 without a propose) */
+    uint32_t* pv_nil;         /* first-wins prevotes for NilValue */
+    uint32_t* pv_validround;  /* first-wins prevotes of (h, propose.valid_round) for the propose's
+                                 value when a propose is logged and valid_round > -1, else 0 */
+    uint8_t* flags;           /* bit 0 a propose is logged, bit 1 it is valid, bit 2 it was traced
+                                 and its signer was new to the trace (never set without bit 1) */
+    uint8_t* bits;            /* the eight predicates above */
+    uint8_t* pclass;          /* n bytes or NULL: the propose classes above */
+    uint8_t* dup;             /* n bytes or NULL: hd_tally_out.dup */
+} hd_decide_out;
+
+/* Host buffers (as hd_tally); in->sched32 and in->value_ok are host pointers.
+ * Whole batch only.  HD_EINVAL for NULL arguments, before any device work;
+ * HD_ECAP with out->n set when out->cap is too small. */
+int hd_decide(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in,
+              hd_decide_out* out);
+/* Device inputs (the batch, the valid bitmap of hd_verify_batch_device,
+ * in->sched32 and in->value_ok are device pointers), host outputs;
+ * synchronises `stream`. */
+int hd_decide_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                            const hd_decide_in* in, hd_decide_out* out, void* stream);
 
 /* ---- multi-GPU in one process ----------------------
  * A context per device plus an RCCL communicator over the devices
