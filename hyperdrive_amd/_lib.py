@@ -105,6 +105,11 @@ class HdDecideOut(ctypes.Structure):
         ("pclass", ctypes.c_void_p), ("dup", ctypes.c_void_p)]
 
 
+class HdDecideOrder(ctypes.Structure):
+    """include/hd_verify.h hd_decide_order (hd_decide_ordered / hd_decide_ordered_device_bitmap)."""
+    _fields_ = [("cap", ctypes.c_uint32), ("when", ctypes.c_void_p), ("exact_until", ctypes.c_void_p)]
+
+
 class HdTallyTicket(ctypes.Structure):
     """include/hd_verify.h hd_tally_ticket (hd_tally_device_bitmap_async / hd_tally_collect)."""
     _fields_ = [("stage", ctypes.c_void_p), ("stage_cap", ctypes.c_size_t), ("dup", ctypes.c_int),
@@ -170,6 +175,12 @@ SIGNATURES = {
     "hd_decide_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
                                                ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
                                                ctypes.c_void_p]),
+    "hd_decide_ordered": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                         ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
+                                         ctypes.POINTER(HdDecideOrder)]),
+    "hd_decide_ordered_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                                       ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
+                                                       ctypes.POINTER(HdDecideOrder), ctypes.c_void_p]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

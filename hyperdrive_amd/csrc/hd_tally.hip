@@ -33,6 +33,9 @@
 // hd_decide (the end of this file) runs the same passes with the propose log
 // of process.go:758-819 beside them -- a fourth claim table P keyed (h, r) --
 // and turns each round's counts into one row with the eight predicate bits.
+// hd_decide_ordered adds a sort of the logged votes by (round, batch index)
+// and a per-row walk that finds the message at which each predicate first
+// holds in batch order.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -51,7 +54,7 @@ using namespace hd;
 static const uint32_t kEmpty = 0xFFFFFFFFu;
 
 struct TallyWork {
-    DevBuf b[21];
+    DevBuf b[24];
     void* host = nullptr;   // pinned download stage (hipHostMalloc)
     size_t host_cap = 0;
     uint32_t* scalar = nullptr;   // pinned word (a partition's candidate count)
@@ -78,9 +81,11 @@ struct TallyWork {
 // on the device instead of staged; T_CHECK: HD_TALLY_CHECK's counters;
 // hd_decide: T_P the propose claim table, T_PSLOT per-item propose slot,
 // T_DSTAGE / T_DOVF its output stage and overflow rows, T_SCHED / T_VOK the
-// host form's uploaded schedule and value_ok bytes
+// host form's uploaded schedule and value_ok bytes; hd_decide_ordered: T_WKEY /
+// T_WVAL the per-item sort keys and batch indices (unsorted | sorted), T_WTMP
+// the radix sort's temporary storage
 enum TSlot { T_G, T_D, T_C, T_GSLOT, T_DSLOT, T_NSEL, T_SEL, T_SORTK, T_SORTV, T_TMP, T_DUP, T_ROUTE, T_CHECK,
-             T_CSLOT, T_BITS, T_P, T_PSLOT, T_DSTAGE, T_DOVF, T_SCHED, T_VOK };
+             T_CSLOT, T_BITS, T_P, T_PSLOT, T_DSTAGE, T_DOVF, T_SCHED, T_VOK, T_WKEY, T_WVAL, T_WTMP };
 
 // table layouts (structure of arrays inside one allocation, capacity cap)
 struct GTab {   // (h, r)
@@ -1803,11 +1808,274 @@ __global__ void k_decide_clean(uint32_t m, const uint32_t* __restrict__ gslot, c
     }
 }
 
+// ---------------------------------------------------------- decide, ordered
+// hd_decide_ordered: per row and predicate the batch index at which the rule
+// first holds when the batch is inserted one message at a time (when[8], and
+// exact_until for the one rule that is not monotone; include/hd_verify.h).
+// Every value is "the k-th smallest batch index among the logged votes of a
+// round that have some property", so the passes run between k_decide_emit and
+// k_decide_clean, while G / C / D / P and the dense cells are still populated:
+//
+//   k_decide_order_keys   every item's sort key: its round's number (G.gid),
+//                         or the key mask for an item that is not a logged
+//                         vote.  Bits 30 and 31, above the sorted bits, carry
+//                         "precommit" and "this vote is its signer's trace
+//                         entry" (the signer's logged vote of the other type
+//                         is absent or later: the other dense cell, or D)
+//   one stable radix sort of (key, batch index) over the key bits: each
+//                         round's logged votes become one segment in arrival
+//                         order, whichever log path they took
+//   k_decide_when         one wavefront per emitted row: finds the round's
+//                         segment (a 64-ary search by the wavefront), walks it
+//                         64 items at a time with ballot / popcount prefixes
+//                         of eight running counts, and records the index at
+//                         which each count reaches its threshold.  Value
+//                         classes compare C slots (an item's cslot against the
+//                         slot of the propose's value), not value bytes.
+#define HD_WKEY_PRECOMMIT 0x40000000u
+#define HD_WKEY_TRACE 0x80000000u
+
+// the D slot of the log (h, r, t, from), kEmpty when there is none
+__device__ __forceinline__ uint32_t log_find(const DevBatch& b, const uint32_t* D, uint32_t mask, int64_t h, int64_t r,
+                                             const uint8_t* from, uint32_t t) {
+    return find(D, mask, hash_log(hash_hr(h, r), from, t), [&](uint32_t c) {
+        return b.type[c] == t && b.height[c] == h && b.round[c] == r && eq32(b.from32 + 32 * (size_t)c, from);
+    });
+}
+
+__global__ void k_decide_order_keys(DevBatch b, uint32_t m, const uint32_t* __restrict__ gslot,
+                                    const uint32_t* __restrict__ cslot, const uint32_t* __restrict__ ref,
+                                    const uint32_t* __restrict__ gid, const uint32_t* __restrict__ Dd, uint32_t S,
+                                    const uint32_t* __restrict__ D, uint32_t mask, uint32_t kmask,
+                                    uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < m; q += stride) {
+        const uint32_t g = gslot[q];
+        uint32_t k = kmask;
+        if (g != kEmpty && cslot[q] != kEmpty) {   // a logged vote (a logged propose has no count slot)
+            const bool pc = b.type[q] == T_PRECOMMIT;
+            const uint32_t rf = ref[q];
+            uint32_t other;   // the signer's logged vote of the other type in the round
+            if (!(rf & HD_REF_HASHED)) {
+                other = Dd[pc ? rf - S : rf + S];
+            } else {
+                const uint32_t o = log_find(b, D, mask, b.height[q], b.round[q], b.from32 + 32 * (size_t)q,
+                                            pc ? T_PREVOTE : T_PRECOMMIT);
+                other = o == kEmpty ? kEmpty : D[o];
+            }
+            k = gid[g] | (pc ? HD_WKEY_PRECOMMIT : 0u) | (other > q ? HD_WKEY_TRACE : 0u);
+        }
+        key[q] = k;
+        val[q] = q;
+    }
+}
+
+// the C slot of (G slot g, type t, value (v0, v1)), kEmpty when no vote carries it
+__device__ __forceinline__ uint32_t cslot_of(const CTab& C, uint32_t mask, const DevBatch& b, const uint32_t* gslot,
+                                             uint32_t g, uint8_t t, uint4 v0, uint4 v1) {
+    const uint64_t hv = ((uint64_t)v0.y << 32 | v0.x) ^ ((uint64_t)v0.w << 32 | v0.z);
+    return find(C.claim, mask, mix64(hv ^ ((uint64_t)g << 1 | (t & 1u))), [&](uint32_t o) {
+        if (gslot[o] != g || b.type[o] != t) return false;
+        const uint4* p = reinterpret_cast<const uint4*>(b.value32 + 32 * (size_t)o);
+        const uint4 a = p[0], d = p[1];
+        return ((a.x ^ v0.x) | (a.y ^ v0.y) | (a.z ^ v0.z) | (a.w ^ v0.w) | (d.x ^ v1.x) | (d.y ^ v1.y) |
+                (d.z ^ v1.z) | (d.w ^ v1.w)) == 0;
+    });
+}
+
+// first position of skey[0..n) whose sorted bits are >= target, by the whole
+// wavefront: 64 probes per step narrow the range 64-fold
+__device__ __forceinline__ uint32_t seg_start(const uint32_t* __restrict__ skey, uint32_t n, uint32_t kmask,
+                                              uint32_t target) {
+    const uint32_t lane = threadIdx.x & 63;
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const uint32_t step = (hi - lo + 63u) / 64u;
+        const uint64_t pos = (uint64_t)lo + (uint64_t)lane * step;
+        const bool less = pos < hi && (skey[pos] & kmask) < target;
+        const uint32_t c = (uint32_t)__popcll(__ballot(less));   // sorted: the lanes below the answer
+        if (c == 0) return lo;
+        const uint64_t nlo = (uint64_t)lo + (uint64_t)(c - 1) * step + 1u, nhi = (uint64_t)lo + (uint64_t)c * step;
+        hi = nhi < hi ? (uint32_t)nhi : hi;
+        lo = (uint32_t)nlo;
+    }
+    return lo;
+}
+
+// Walks a segment of the sorted items in arrival order.  flags_of(idx, key,
+// cslot) gives an item's NC class bits; res[k] becomes, on the lane that holds
+// it, the batch index of the item at which class k's running count equals
+// target[k].  Four 64-item chunks are loaded before any is counted, so that a
+// long segment pays the gather latency once per 256 items.
+template <int NC, typename F>
+__device__ __forceinline__ void seg_walk(const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sval,
+                                         const uint32_t* __restrict__ cslot, uint32_t start, uint32_t len, F flags_of,
+                                         const uint64_t (&target)[NC], uint32_t (&res)[NC]) {
+    const uint32_t lane = threadIdx.x & 63;
+    const unsigned long long le = (2ull << lane) - 1ull;   // this lane and the lanes below it
+    uint32_t cnt[NC];
+    HD_UNROLL for (int k = 0; k < NC; k++) cnt[k] = 0;
+    for (uint32_t base = 0; base < len; base += 256u) {
+        uint32_t key[4], idx[4], cs[4];
+        HD_UNROLL for (int u = 0; u < 4; u++) {
+            const uint32_t j = base + 64u * u + lane;
+            key[u] = j < len ? skey[(size_t)start + j] : 0u;
+            idx[u] = j < len ? sval[(size_t)start + j] : 0u;
+        }
+        HD_UNROLL for (int u = 0; u < 4; u++) {
+            const uint32_t j = base + 64u * u + lane;
+            cs[u] = j < len ? cslot[idx[u]] : kEmpty;
+        }
+        HD_UNROLL for (int u = 0; u < 4; u++) {
+            const uint32_t j = base + 64u * u + lane;
+            const uint32_t fl = j < len ? flags_of(idx[u], key[u], cs[u]) : 0u;
+            HD_UNROLL for (int k = 0; k < NC; k++) {
+                const bool f = (fl >> k) & 1u;
+                const unsigned long long bal = __ballot(f);
+                if (f && (uint64_t)(cnt[k] + (uint32_t)__popcll(bal & le)) == target[k]) res[k] = idx[u];
+                cnt[k] += (uint32_t)__popcll(bal);
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+    for (int d = 32; d > 0; d >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, d, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(256) void k_decide_when(DevBatch b, uint32_t m, DecideIn in,
+                                                     const uint32_t* __restrict__ gslot,
+                                                     const uint32_t* __restrict__ cslot, GTab G, CTab C,
+                                                     const uint32_t* __restrict__ D, const uint32_t* __restrict__ Dd,
+                                                     AdmIndex ix, uint32_t S, uint32_t nd, uint32_t mask,
+                                                     const uint32_t* __restrict__ skey,
+                                                     const uint32_t* __restrict__ sval, uint32_t kmask, DecideCols st,
+                                                     uint32_t H, DecideCols ov, const uint32_t* stage_hdr,
+                                                     uint32_t* __restrict__ st_when, uint32_t* __restrict__ st_until,
+                                                     uint32_t* __restrict__ ov_when, uint32_t* __restrict__ ov_until) {
+    const uint32_t rows = stage_hdr[0];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t nwaves = gridDim.x * (blockDim.x >> 6);
+    const uint64_t q2 = 2ull * in.f + 1ull, q1 = (uint64_t)in.f + 1ull;
+    const uint32_t never = HD_WHEN_NEVER;
+    for (uint32_t pos = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); pos < rows; pos += nwaves) {
+        const DecideCols& x = pos < H ? st : ov;
+        const uint32_t j = pos < H ? pos : pos - H;
+        uint32_t* const o_when = (pos < H ? st_when : ov_when) + 8 * (size_t)j;
+        uint32_t* const o_until = (pos < H ? st_until : ov_until) + j;
+        const uint32_t bits = x.bits[j];
+        uint32_t w[8] = {never, never, never, never, never, never, never, never}, until = never;
+        if (bits) {   // no bit set: nothing ever held (bit 2 covers the exact rule's window)
+            const uint32_t g = gslot[x.rep[j]], p = x.propose[j], flags = x.flags[j];
+            const int64_t h = x.h[j], r = x.r[j];
+            const uint32_t len = x.prevotes[j] + x.precommits[j];
+            const bool valid = (flags & 2u) != 0;
+            const uint4 zero = make_uint4(0, 0, 0, 0);
+            uint4 v0 = zero, v1 = zero;
+            if (p != kEmpty) {
+                const uint4* vp = reinterpret_cast<const uint4*>(b.value32 + 32 * (size_t)p);
+                v0 = vp[0];
+                v1 = vp[1];
+            }
+            // the C slots an item's cslot is compared with (kEmpty matches no logged vote)
+            const uint32_t c_nil = (bits & 2u) ? cslot_of(C, mask, b, gslot, g, T_PREVOTE, zero, zero) : kEmpty;
+            const uint32_t c_pv = (bits & (32u | 128u)) ? cslot_of(C, mask, b, gslot, g, T_PREVOTE, v0, v1) : kEmpty;
+            const uint32_t c_pc = (bits & 64u) ? cslot_of(C, mask, b, gslot, g, T_PRECOMMIT, v0, v1) : kEmpty;
+            // the proposer's trace entry (process.go:813-816): the propose when it comes before the
+            // proposer's first logged vote of the round, which then is no entry of its own
+            bool addp = false;
+            uint32_t fv = kEmpty;
+            if ((bits & 16u) && valid) {
+                if (!(flags & 4u)) {   // the proposer has logged votes in the round
+                    const uint32_t rid = G.gid[g];
+                    int32_t signer = -1;
+                    if (rid < nd) {
+                        uint32_t from_be[8];
+                        load_row32_be(from_be, b.from32, p);
+                        signer = adm_index_find(ix, from_be);
+                    }
+                    if (signer >= 0) {
+                        const uint32_t cell = rid * 2u * S + (uint32_t)signer;
+                        fv = min(Dd[cell], Dd[cell + S]);
+                    } else {
+                        const uint8_t* from = b.from32 + 32 * (size_t)p;
+                        const uint32_t a = log_find(b, D, mask, h, r, from, T_PREVOTE),
+                                       c = log_find(b, D, mask, h, r, from, T_PRECOMMIT);
+                        fv = min(a == kEmpty ? kEmpty : D[a], c == kEmpty ? kEmpty : D[c]);
+                    }
+                }
+                addp = p < fv;
+            }
+            uint32_t res[8] = {never, never, never, never, never, never, never, never};
+            if (len) {
+                const uint64_t target[8] = {q2, q2, q2, q2 + 1ull, q1 - 1ull, q1, q2, q2};
+                const uint32_t start = seg_start(skey, m, kmask, G.gid[g]);
+                seg_walk<8>(skey, sval, cslot, start, min(len, m - start),
+                            [&](uint32_t idx, uint32_t key, uint32_t cs) {
+                                const bool pc = (key & HD_WKEY_PRECOMMIT) != 0;
+                                const bool tn = (key & HD_WKEY_TRACE) != 0 && !(addp && idx == fv);
+                                return (pc ? 0u : 1u) | (cs == c_nil ? 2u : 0u) | (pc ? 4u | 8u : 0u) |
+                                       (tn ? 16u | 32u : 0u) | (cs == c_pv ? 64u : 0u) | (cs == c_pc ? 128u : 0u);
+                            },
+                            target, res);
+                HD_UNROLL for (int k = 0; k < 8; k++) res[k] = wave_min(res[k]);
+            }
+            w[0] = res[0];
+            w[1] = res[1];
+            w[2] = w[3] = res[2];
+            until = res[3];
+            // the q1-th smallest trace entry: the votes' entries with the propose merged in at p
+            if (!addp) {
+                w[4] = res[5];
+            } else if (q1 == 1ull) {
+                w[4] = min(p, res[5]);
+            } else if (res[4] != never) {   // the (q1-1)-th vote entry exists
+                w[4] = p < res[4] ? res[4] : min(p, res[5]);
+            }
+            if (valid && res[6] != never) w[5] = max(p, res[6]);
+            if (valid && res[7] != never) w[6] = max(p, res[7]);
+            if (bits & 128u) {   // the valid round's prevotes for the propose's value (process.go:486-491)
+                const int64_t vr = b.valid_round[p];
+                uint32_t k7 = res[6];
+                if (vr != r) {
+                    const uint32_t g2 = find(G.claim, mask, hash_hr(h, vr),
+                                             [&](uint32_t o) { return b.height[o] == h && b.round[o] == vr; });
+                    k7 = never;
+                    if (g2 != kEmpty) {
+                        const uint32_t c_vr = cslot_of(C, mask, b, gslot, g2, T_PREVOTE, v0, v1);
+                        const uint64_t target1[1] = {q2};
+                        uint32_t res1[1] = {never};
+                        const uint32_t start2 = seg_start(skey, m, kmask, G.gid[g2]);
+                        seg_walk<1>(skey, sval, cslot, start2, min(G.nprev[g2] + G.nprec[g2], m - start2),
+                                    [&](uint32_t, uint32_t, uint32_t cs) { return cs == c_vr ? 1u : 0u; }, target1,
+                                    res1);
+                        k7 = wave_min(res1[0]);
+                    }
+                }
+                if (k7 != never) w[7] = max(p, k7);
+            }
+        }
+        if (lane == 0) {
+            uint4* o = reinterpret_cast<uint4*>(o_when);
+            o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+            o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+            *o_until = until;
+        }
+    }
+}
+
 static size_t decide_pad(size_t n) { return (n + 63) & ~(size_t)63; }
 
 static bool decide_out_ok(const hd_decide_out* o) {
     return o && o->height && o->round && o->rep && o->propose && o->prevotes && o->precommits && o->trace &&
            o->pv_value && o->pc_value && o->pv_nil && o->pv_validround && o->flags && o->bits;
+}
+
+// the ordered form's second output: rows for every row of `out`; the sort keys keep bits 30 and 31
+// for flags, so a batch has fewer than 2^30 messages
+static bool decide_order_ok(const hd_decide_out* o, const hd_decide_order* w, uint32_t n) {
+    return o && w && w->when && w->exact_until && w->cap >= o->cap && n < (1u << 30);
 }
 
 static void decide_unpack(const DecideCols& x, uint32_t rows, uint32_t at, hd_decide_out* out) {
@@ -1826,9 +2094,11 @@ static void decide_unpack(const DecideCols& x, uint32_t rows, uint32_t at, hd_de
 // Whole batch only (items = batch indices).  One download of the stage
 // [rows | dup (n bytes, when asked) | pclass (n bytes, when asked) | rows at
 // capacity H]; rows past H come from the overflow columns by a second round
-// of copies.
+// of copies.  With `ord` (hd_decide_ordered) the stage continues with
+// [when (8 words per row) | exact_until] at capacity H, and the overflow
+// buffer likewise after its rows.
 static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap,
-                         DecideIn in, hd_decide_out* out, hipStream_t s) {
+                         DecideIn in, hd_decide_out* out, hipStream_t s, hd_decide_order* ord = nullptr) {
     const uint32_t n = hb->n, m = n;
     if (!ctx->tally) ctx->tally = new TallyWork();
     TallyWork* tw = ctx->tally;
@@ -1838,7 +2108,8 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
     const uint32_t H = tw->guess_dec;
     const size_t dup_off = 64, pc_off = dup_off + (out->dup ? decide_pad(n) : 0),
                  rows_off = pc_off + (out->pclass ? decide_pad(n) : 0);
-    const size_t total = rows_off + HD_DECIDE_ROW_BYTES * (size_t)H + 64;
+    const size_t when_off = rows_off + decide_pad(HD_DECIDE_ROW_BYTES * (size_t)H), until_off = when_off + 32 * (size_t)H;
+    const size_t total = ord ? until_off + 4 * (size_t)H + 64 : rows_off + HD_DECIDE_ROW_BYTES * (size_t)H + 64;
     char* st = (char*)tbuf(ctx, T_DSTAGE, total, &rc);
     if (rc) return rc;
     uint8_t* d_dup = out->dup ? (uint8_t*)(st + dup_off) : nullptr;
@@ -1859,11 +2130,27 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
     uint32_t* bits = (uint32_t*)tbuf(ctx, T_BITS, 4 * (4 * nw + 2 * (size_t)nbo), &rc);
     uint32_t* P = (uint32_t*)tbuf(ctx, T_P, 4 * K, &rc);
     uint32_t* pslot = (uint32_t*)tbuf(ctx, T_PSLOT, 4 * (size_t)m, &rc);
-    char* ovf = (char*)tbuf(ctx, T_DOVF, HD_DECIDE_ROW_BYTES * (size_t)m + 64, &rc);
+    const size_t ovw_off = decide_pad(HD_DECIDE_ROW_BYTES * (size_t)m + 64), ovu_off = ovw_off + 32 * (size_t)m;
+    char* ovf = (char*)tbuf(ctx, T_DOVF, ord ? ovu_off + 4 * (size_t)m + 64 : HD_DECIDE_ROW_BYTES * (size_t)m + 64, &rc);
     const uint32_t S = ctx->n_adm;
     const size_t dcap = S > 0 ? std::min<size_t>(HD_TALLY_DENSE_MAX, (size_t)m * 2 * S) : 0;
     const uint32_t nd = S > 0 ? (uint32_t)(dcap / (2 * (size_t)S)) : 0u;
     uint32_t* Dd = dcap ? (uint32_t*)tbuf(ctx, T_C, 4 * dcap, &rc) : nullptr;
+    // the ordered form's sort: keys over the bits that hold every round number and, above them, the
+    // key of the items that are no logged vote
+    uint32_t *wkey = nullptr, *wval = nullptr, kbits = 1;
+    void* wtmp = nullptr;
+    size_t wtmp_bytes = 0;
+    if (ord) {
+        while ((1ull << kbits) <= m) kbits++;
+        wkey = (uint32_t*)tbuf(ctx, T_WKEY, 8 * (size_t)m, &rc);
+        wval = (uint32_t*)tbuf(ctx, T_WVAL, 8 * (size_t)m, &rc);
+        if (rc) return rc;
+        TCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, wtmp_bytes, wkey, wkey + m, wval, wval + m, (int)m, 0,
+                                                (int)kbits, s),
+             "decide sort size");
+        wtmp = tbuf(ctx, T_WTMP, wtmp_bytes + 64, &rc);
+    }
     if (rc) return rc;
     uint32_t* tabs = (uint32_t*)tb;
     GTab G{tabs, tabs + 3 * K, tabs + 4 * K, tabs + 5 * K, tabs + 7 * K};
@@ -1906,6 +2193,19 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
         HD_DECIDE_ORDER(2048u)
 #undef HD_DECIDE_ORDER
     }
+    if (ord) {   // between the emit and the clean: the tables are populated and read-only
+        const uint32_t kmask = (uint32_t)((1ull << kbits) - 1ull);
+        k_decide_order_keys<<<grid, 256, 0, s>>>(b, m, gslot, cslot, ref, G.gid, Dd, S, d, mask, kmask, wkey, wval);
+        TCHK(hipGetLastError(), "decide order keys");
+        TCHK(hipcub::DeviceRadixSort::SortPairs(wtmp, wtmp_bytes, wkey, wkey + m, wval, wval + m, (int)m, 0,
+                                                (int)kbits, s),
+             "decide sort");
+        const uint32_t wgrid = std::min<uint32_t>((m + 3) / 4, (uint32_t)ctx->n_cu * 8u);   // four rows per block
+        k_decide_when<<<wgrid, 256, 0, s>>>(b, m, in, gslot, cslot, G, C, d, Dd, ix, S, nd, mask, wkey + m, wval + m,
+                                            kmask, sc, H, oc, (const uint32_t*)st, (uint32_t*)(st + when_off),
+                                            (uint32_t*)(st + until_off), (uint32_t*)(ovf + ovw_off),
+                                            (uint32_t*)(ovf + ovu_off));
+    }
     k_decide_clean<<<grid, 256, 0, s>>>(m, gslot, cslot, ref, pslot, G, C, d, P, Bg, ctr);
     TCHK(hipGetLastError(), "decide order kernels");
     tw->dirty = tw->pdirty = false;
@@ -1926,6 +2226,10 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
     if (out->dup) memcpy(out->dup, hs + dup_off, n);
     if (out->pclass) memcpy(out->pclass, hs + pc_off, n);
     decide_unpack(decide_cols(const_cast<char*>(hs) + rows_off, H), std::min(rows, H), 0, out);
+    if (ord) {
+        memcpy(ord->when, hs + when_off, 32 * (size_t)std::min(rows, H));
+        memcpy(ord->exact_until, hs + until_off, 4 * (size_t)std::min(rows, H));
+    }
     if (rows > H) {   // more rounds than staged: the overflow columns, straight into out
         const uint32_t e = rows - H;
         struct Piece {
@@ -1942,14 +2246,20 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
             {out->flags + H, oc.flags, (size_t)e},            {out->bits + H, oc.bits, (size_t)e},
         };
         for (const Piece& p : pieces) TCHK(hipMemcpyAsync(p.dst, p.src, p.sz, hipMemcpyDeviceToHost, s), "decide overflow");
+        if (ord) {
+            TCHK(hipMemcpyAsync(ord->when + 8 * (size_t)H, ovf + ovw_off, 32 * (size_t)e, hipMemcpyDeviceToHost, s),
+                 "decide overflow when");
+            TCHK(hipMemcpyAsync(ord->exact_until + H, ovf + ovu_off, 4 * (size_t)e, hipMemcpyDeviceToHost, s),
+                 "decide overflow until");
+        }
         TCHK(hipStreamSynchronize(s), "decide overflow sync");
     }
     return HD_OK;
 }
 
-extern "C" {
-
-int hd_decide(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in, hd_decide_out* out) {
+// hd_decide and hd_decide_ordered (ord non-NULL and checked by the caller)
+static int decide_host(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in,
+                       hd_decide_out* out, hd_decide_order* ord) {
     if (!ctx || !batch || !verdict || !in || !decide_out_ok(out)) return HD_EINVAL;
     if (!batch->type || !batch->height || !batch->round || !batch->value32 || !batch->from32) return HD_EINVAL;
     if (in->sched32 && in->n_sched == 0) return HD_EINVAL;
@@ -1981,11 +2291,11 @@ int hd_decide(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const 
         TCHK(hipMemcpyAsync(p, in->value_ok, n, hipMemcpyHostToDevice, ctx->stream), "value_ok upload");
         di.value_ok = p;
     }
-    return decide_device(ctx, &db, d_v, nullptr, di, out, ctx->stream);
+    return decide_device(ctx, &db, d_v, nullptr, di, out, ctx->stream, ord);
 }
 
-int hd_decide_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
-                            const hd_decide_in* in, hd_decide_out* out, void* stream) {
+static int decide_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap, const hd_decide_in* in,
+                         hd_decide_out* out, void* stream, hd_decide_order* ord) {
     if (!ctx || !dbatch || !in || !decide_out_ok(out)) return HD_EINVAL;
     if (dbatch->n && (!d_valid_bitmap || !dbatch->type || !dbatch->height || !dbatch->round || !dbatch->value32 ||
                       !dbatch->from32))
@@ -1995,7 +2305,31 @@ int hd_decide_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t*
     if (dbatch->n == 0) return HD_OK;
     (void)hipSetDevice(ctx->device);
     return decide_device(ctx, dbatch, nullptr, d_valid_bitmap, DecideIn{in->f, in->n_sched, in->sched32, in->value_ok},
-                         out, stream ? (hipStream_t)stream : ctx->stream);
+                         out, stream ? (hipStream_t)stream : ctx->stream, ord);
+}
+
+extern "C" {
+
+int hd_decide(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in, hd_decide_out* out) {
+    return decide_host(ctx, batch, verdict, in, out, nullptr);
+}
+
+int hd_decide_ordered(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in,
+                      hd_decide_out* out, hd_decide_order* order) {
+    if (!decide_order_ok(out, order, batch ? batch->n : 0u)) return HD_EINVAL;
+    return decide_host(ctx, batch, verdict, in, out, order);
+}
+
+int hd_decide_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                            const hd_decide_in* in, hd_decide_out* out, void* stream) {
+    return decide_bitmap(ctx, dbatch, d_valid_bitmap, in, out, stream, nullptr);
+}
+
+int hd_decide_ordered_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                    const hd_decide_in* in, hd_decide_out* out, hd_decide_order* order,
+                                    void* stream) {
+    if (!decide_order_ok(out, order, dbatch ? dbatch->n : 0u)) return HD_EINVAL;
+    return decide_bitmap(ctx, dbatch, d_valid_bitmap, in, out, stream, order);
 }
 
 }  // extern "C"

@@ -12,6 +12,10 @@ later ones included, and the caller applies ``valid_round < CurrentRound``.
 ``Verifier.decide`` (hd_decide) evaluates the same eight predicates on the
 device for every round of a batch, with the propose taken from the batch's own
 propose log (process.go:758-819); its ``decisions`` are these dicts.
+``Verifier.decide_ordered`` (hd_decide_ordered) adds the batch index at which
+each predicate first holds in batch order, for every height of the batch and
+for proposes too: the per-message crossing that is otherwise only available
+from the host vote table (hd_votes' events, one height at a time).
 """
 from __future__ import annotations
 
@@ -39,7 +43,8 @@ def decide(tally, height: int, round_: int, f: int, propose_value: Optional[byte
     - precommit_nil     L44 #prevotes for NilValue >= 2f+1          process.go:626-632
     - timeout_precommit_reached  L47: the log reached 2f+1 at some insert of
       the batch (``>=``: true iff the equality ``len == 2f+1`` held at the
-      crossing insert; the per-insert crossing is hd_votes' EV_PRECOMMIT_2F1)
+      crossing insert; the per-insert crossing is hd_votes' EV_PRECOMMIT_2F1,
+      or ``when[3]`` / ``exact_until`` of ``Verifier.decide_ordered``)
                                                                     process.go:658
     - timeout_precommit_exact  L47 as StartRound evaluates it on entering the
       round: ``len(PrecommitLogs[r]) == 2f+1`` exactly (more than 2f+1

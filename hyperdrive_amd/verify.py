@@ -20,7 +20,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -211,6 +211,28 @@ class DecideResult:
         """{(h, r): batch index of the logged propose}."""
         return {(int(h), int(r)): int(p) for h, r, p in zip(self.height, self.round, self.propose)
                 if int(p) != NO_PROPOSE}
+
+
+WHEN_NEVER = 0xFFFFFFFF
+
+
+@dataclass
+class OrderedDecideResult(DecideResult):
+    """A DecideResult plus, per row and predicate, the batch index at which the
+    predicate first holds when the batch is inserted one message at a time
+    (hd_decide_order, include/hd_verify.h)."""
+    when: np.ndarray = None          # uint32[rows, 8], WHEN_NEVER where the predicate never holds
+    exact_until: np.ndarray = None   # uint32[rows]: timeout_precommit_exact holds on [when[:, 3], exact_until)
+
+    @property
+    def firings(self) -> List[Tuple[int, int, int, str]]:
+        """(batch index, height, round, DECISION_KEYS name) of every predicate
+        that ever holds, sorted by batch index, then bit: the order in which
+        to feed the automaton."""
+        rows, ks = np.nonzero(self.when != WHEN_NEVER)
+        out = [(int(self.when[j, k]), int(k), int(self.height[j]), int(self.round[j])) for j, k in zip(rows, ks)]
+        out.sort(key=lambda x: (x[0], x[1]))
+        return [(i, h, r, DECISION_KEYS[k]) for i, k, h, r in out]
 
 
 class Verifier:
@@ -525,6 +547,78 @@ class Verifier:
         self._check(self._lib.hd_decide_device_bitmap(self._ctx, ctypes.byref(dbatch), d_bitmap, ctypes.byref(cin),
                                                       ctypes.byref(o), stream), "hd_decide_device_bitmap")
         return self._decide_result(n, o, a)
+
+    # ---- decide, ordered ---------------------------------------------
+    @staticmethod
+    def _order_struct(cap: int):
+        from ._lib import HdDecideOrder
+        when = np.full((max(cap, 1), 8), WHEN_NEVER, np.uint32)
+        until = np.full(max(cap, 1), WHEN_NEVER, np.uint32)
+        w = HdDecideOrder()
+        w.cap = cap
+        w.when = _ptr(when)
+        w.exact_until = _ptr(until)
+        return w, when, until
+
+    @staticmethod
+    def _ordered_result(n: int, o, a, when, until) -> OrderedDecideResult:
+        rows = {k: a[k][: o.n].copy() for k in type(o).ROW_FIELDS}
+        return OrderedDecideResult(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), when=when[: o.n].copy(),
+                                   exact_until=until[: o.n].copy(), **rows)
+
+    def decide_ordered(self, batch: Batch, verdict: np.ndarray, f: int, schedule=None,
+                       value_ok=None) -> OrderedDecideResult:
+        """hd_decide_ordered: :meth:`decide` plus the batch index at which each
+        round's predicates first hold in batch order (``when``,
+        ``exact_until``, ``firings``).  Arguments as :meth:`decide`."""
+        from ._lib import HdDecideIn
+        n = len(batch)
+        verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
+        if len(verdict) != n:
+            raise ValueError("verdict length mismatch")
+        sched = _as_rows(schedule, 32) if schedule is not None else None
+        if sched is not None and len(sched) == 0:
+            raise ValueError("an empty schedule (pass None for no turn check)")
+        vok = np.ascontiguousarray(value_ok, dtype=np.uint8) if value_ok is not None else None
+        if vok is not None and len(vok) != n:
+            raise ValueError("value_ok length mismatch")
+        o, a = self._decide_struct(n)
+        w, when, until = self._order_struct(n)
+        cin = HdDecideIn(int(f), len(sched) if sched is not None else 0, _ptr(sched), _ptr(vok))
+        cb = batch.c_struct()
+        self._check(self._lib.hd_decide_ordered(self._ctx, ctypes.byref(cb), _ptr(verdict), ctypes.byref(cin),
+                                                ctypes.byref(o), ctypes.byref(w)), "hd_decide_ordered")
+        return self._ordered_result(n, o, a, when, until)
+
+    def decide_ordered_device(self, dbatch: HdBatch, d_bitmap: int, f: int, schedule=None, value_ok=None,
+                              stream: Optional[int] = None) -> OrderedDecideResult:
+        """hd_decide_ordered_device_bitmap; arguments as :meth:`decide_device`."""
+        import torch
+        from ._lib import HdDecideIn
+        n = dbatch.n
+
+        def dev(x, width):
+            if x is None or isinstance(x, torch.Tensor):
+                return x
+            arr = _as_rows(x, width) if width > 1 else np.ascontiguousarray(x, dtype=np.uint8)
+            t = torch.from_numpy(arr).cuda()
+            torch.cuda.current_stream().synchronize()
+            return t
+
+        sched, vok = dev(schedule, 32), dev(value_ok, 1)
+        if sched is not None and sched.numel() == 0:
+            raise ValueError("an empty schedule (pass None for no turn check)")
+        if vok is not None and vok.numel() != n:
+            raise ValueError("value_ok length mismatch")
+        o, a = self._decide_struct(n)
+        w, when, until = self._order_struct(n)
+        cin = HdDecideIn(int(f), sched.numel() // 32 if sched is not None else 0,
+                         sched.data_ptr() if sched is not None else None,
+                         vok.data_ptr() if vok is not None else None)
+        self._check(self._lib.hd_decide_ordered_device_bitmap(self._ctx, ctypes.byref(dbatch), d_bitmap,
+                                                              ctypes.byref(cin), ctypes.byref(o), ctypes.byref(w),
+                                                              stream), "hd_decide_ordered_device_bitmap")
+        return self._ordered_result(n, o, a, when, until)
 
     # ---- synthetic workload ------------------------------------------
     def gen_keys(self, S: int) -> Tuple[np.ndarray, np.ndarray]:

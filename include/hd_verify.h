@@ -27,6 +27,10 @@
  *   hd_decide           the same plus the propose log (insertPropose,
  *                       process.go:758-819) and the rules' count predicates
  *                       themselves, one row per (height, round).
+ *   hd_decide_ordered   the same plus, per rule, the message at which it first
+ *                       holds when the batch is inserted one message at a
+ *                       time (the rules are tried after every insert,
+ *                       process.go:229-269).
  *
  * Ownership: all host buffers are caller-owned; the library copies what it
  * needs and keeps no pointer after a call returns.  Device buffers passed to
@@ -491,6 +495,47 @@ int hd_decide(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const 
  * synchronises `stream`. */
 int hd_decide_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
                             const hd_decide_in* in, hd_decide_out* out, void* stream);
+
+/* ---- decide, ordered: the message at which each rule fires ----------------
+ * The reference inserts one message at a time and tries its rules after every
+ * insert (process.go:229-269); hd_decide's bits describe only the batch's
+ * final logs.  The ordered form adds, per row and predicate, the batch index
+ * at which the predicate FIRST holds when the batch is inserted in batch
+ * order.  The log after messages 0..i is the final log restricted to indices
+ * <= i (first-wins is "lowest batch index"), so with q2 = 2f+1, q1 = f+1 (in
+ * 64 bits), p the logged propose's index and "k-th" the k-th smallest index:
+ *   when[0]  q2-th logged prevote of the round
+ *   when[1]  q2-th logged prevote of the round for NilValue
+ *   when[2]  q2-th logged precommit of the round
+ *   when[3]  == when[2]: the equality first holds there; it holds on the
+ *            prefixes ending in [when[3], exact_until), exact_until being the
+ *            (q2+1)-th logged precommit of the round
+ *   when[4]  q1-th smallest trace entry; a signer's entry is the lowest of its
+ *            logged prevote, its logged precommit and, for the From of a valid
+ *            logged propose, p
+ *   when[5]  valid propose: max(p, q2-th logged prevote for its value)
+ *   when[6]  valid propose: max(p, q2-th logged precommit for its value)
+ *   when[7]  propose with valid_round > -1: max(p, q2-th logged prevote of
+ *            (h, valid_round) for its value) -- possibly a message of another
+ *            round
+ * HD_WHEN_NEVER where the predicate never holds.  For every bit but 3,
+ * when[k] != HD_WHEN_NEVER exactly when hd_decide's bit k is set; bit 3 is
+ * set exactly when when[3] != HD_WHEN_NEVER and exact_until == HD_WHEN_NEVER.
+ * Sorting the non-NEVER entries by index gives the order in which to feed the
+ * automaton.  Row j belongs to row j of the hd_decide_out, which is filled
+ * exactly as hd_decide fills it.  Errors as hd_decide; order->cap < out->cap
+ * (or a batch of 2^30 messages or more) is HD_EINVAL before any device work. */
+#define HD_WHEN_NEVER 0xFFFFFFFFu
+typedef struct {
+    uint32_t cap;          /* rows of the arrays below; must be >= out->cap */
+    uint32_t* when;        /* cap x 8, row-major: when[8*j + k] for row j, bit k */
+    uint32_t* exact_until; /* cap */
+} hd_decide_order;
+int hd_decide_ordered(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in,
+                      hd_decide_out* out, hd_decide_order* order);
+int hd_decide_ordered_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                    const hd_decide_in* in, hd_decide_out* out, hd_decide_order* order,
+                                    void* stream);
 
 /* ---- multi-GPU in one process ----------------------
  * A context per device plus an RCCL communicator over the devices
