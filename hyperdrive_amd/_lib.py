@@ -110,6 +110,12 @@ class HdDecideOrder(ctypes.Structure):
     _fields_ = [("cap", ctypes.c_uint32), ("when", ctypes.c_void_p), ("exact_until", ctypes.c_void_p)]
 
 
+class HdLogInfo(ctypes.Structure):
+    """include/hd_log.h hd_log_info (hd_log_insert / hd_log_insert_device_bitmap)."""
+    _fields_ = [("base", ctypes.c_uint32), ("kept", ctypes.c_uint32), ("relogged", ctypes.c_uint32),
+                ("logpos", ctypes.c_void_p)]
+
+
 class HdTallyTicket(ctypes.Structure):
     """include/hd_verify.h hd_tally_ticket (hd_tally_device_bitmap_async / hd_tally_collect)."""
     _fields_ = [("stage", ctypes.c_void_p), ("stage_cap", ctypes.c_size_t), ("dup", ctypes.c_int),
@@ -181,6 +187,20 @@ SIGNATURES = {
     "hd_decide_ordered_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
                                                        ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
                                                        ctypes.POINTER(HdDecideOrder), ctypes.c_void_p]),
+    # include/hd_log.h
+    "hd_log_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "hd_log_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hd_log_reset": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32, ctypes.c_void_p,
+                                    ctypes.c_uint32, ctypes.c_uint32]),
+    "hd_log_len": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                  ctypes.POINTER(ctypes.c_uint32)]),
+    "hd_log_insert": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.POINTER(HdDecideOut), ctypes.POINTER(HdDecideOrder),
+                                     ctypes.POINTER(HdLogInfo)]),
+    "hd_log_insert_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                                   ctypes.c_void_p, ctypes.POINTER(HdDecideOut),
+                                                   ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
+                                                   ctypes.c_void_p]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

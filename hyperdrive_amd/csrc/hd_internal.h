@@ -95,6 +95,29 @@ int hd_tally_routed_dup_device(hd_ctx* ctx, const hd_batch* dbatch, const uint32
                                uint8_t* dup_global, hipStream_t s);
 void hd_host_release(hd_ctx* ctx);
 
+// hd_decide's device form (hd_tally.hip), shared with the retained log (hd_log.hip)
+struct DecideIn {
+    uint32_t f, n_sched;
+    const uint8_t* sched32;    // device
+    const uint8_t* value_ok;   // device
+};
+// A caller that keeps the per-message classes on the device: dup and pclass are
+// written to d_dup / d_pclass (n bytes each) and neither is staged or
+// downloaded (out->dup and out->pclass are not read); `queued` runs once every
+// launch of the call is queued on the stream, before the stage's download and
+// the call's one synchronisation, so what it queues is complete on return.
+struct DecideExt {
+    uint8_t* d_dup;
+    uint8_t* d_pclass;
+    int (*queued)(void* arg, hipStream_t s);
+    void* arg;
+};
+// Whole batch only; device batch, verdict bytes or valid bitmap, in.sched32 and
+// in.value_ok; host outputs; synchronises s.  ord: the ordered form's output
+// or NULL; ext: NULL for hd_decide* themselves.
+int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap, DecideIn in,
+                  hd_decide_out* out, hipStream_t s, hd_decide_order* ord, const DecideExt* ext);
+
 // known-key fast path (hd_fastverify.hip)
 int hd_fb_init(hd_ctx* ctx);                    // tables of G (slot 0); at context creation
 void hd_fb_release(hd_ctx* ctx);

@@ -1,0 +1,443 @@
+// hd_log.hip -- a height's vote and propose logs retained on the device
+// across decide calls (include/hd_log.h).
+//
+// The log is a structure of arrays in HBM holding, in arrival order, the
+// messages the reference keeps in ProposeLogs / PrevoteLogs / PrecommitLogs
+// (every logged vote and logged propose of the height).  One insert of a batch
+// of n messages behind L retained entries:
+//
+//   k_log_append   one lane per joined position: a new message's fields are
+//                  copied behind the retained entries (positions L .. L+n-1)
+//                  and every position gets its verdict byte -- a retained entry
+//                  is VALID, a new message only when its verdict / bitmap bit
+//                  says so and its height is the log's -- and value_ok byte
+//   hd_decide_run  the ordered decide passes over the L + n items
+//                  (hd_tally.hip), with dup / pclass left on the device
+//   k_log_count    per block of 256 joined positions: how many retained
+//                  entries came out logged again and how many new messages are
+//                  kept (dup == 0 or pclass == 0); ballot / popcount per
+//                  wavefront, the block's two totals through LDS
+//   k_log_keep     a stable compaction of the kept new messages: a block's
+//                  offset is the sum of the preceding blocks' totals (as
+//                  k_tally_emit sums its offsets: no ticket, no device-scope
+//                  release), a lane's the ballot prefix inside its wavefront
+//                  plus the wavefronts before it.  Kept rows go to a second
+//                  buffer -- compacting in place would let one block overwrite
+//                  rows another has not read -- and k_log_commit copies them back
+//                  behind the retained entries once the host has accepted the
+//                  insert (stream-ordered before the next call).  The
+//                  pass also fills logpos and gathers the batch's dup / pclass
+//                  bytes next to it, so the insert downloads one small block.
+//
+// The host reads [kept, relogged | logpos | dup | pclass] from a pinned stage
+// after the decide's one synchronisation; the log's length moves only after
+// every check has passed, so any error leaves the log as it was.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <new>
+
+#include "../../include/hd_log.h"
+#include "hd_internal.h"
+
+using namespace hd;
+
+#define HD_LOG_NOT_CANDIDATE 0xFFu   // verdict byte of a new message that is not VALID or not of the log's height
+
+struct LogCols {
+    uint8_t* type;
+    int64_t* height;
+    int64_t* round;
+    int64_t* vround;
+    uint8_t* value32;
+    uint8_t* from32;
+    uint8_t* vok;
+};
+static const size_t kLogWidth[7] = {1, 8, 8, 8, 32, 32, 1};
+static void** log_col(LogCols& c, int k) {
+    void** p[7] = {(void**)&c.type, (void**)&c.height, (void**)&c.round, (void**)&c.vround,
+                   (void**)&c.value32, (void**)&c.from32, (void**)&c.vok};
+    return p[k];
+}
+
+struct hd_log {
+    hd_ctx* ctx = nullptr;
+    int device = 0;
+    int64_t height = 0;
+    uint32_t f = 0, n_sched = 0, max_entries = 0;
+    uint32_t L = 0;               // retained entries
+    uint8_t* d_sched = nullptr;
+    size_t cap_sched = 0;
+    LogCols lg{};                 // retained entries, then the call's batch: cap_items rows
+    size_t cap_items = 0;
+    DevBuf vd, dup, pclass;       // per joined position: verdict and the decide's classes
+    LogCols tmp{};                // the kept rows of one insert: cap_new rows
+    size_t cap_new = 0;
+    DevBuf blk;                   // two totals per block of 256 joined positions
+    DevBuf res;                   // [kept, relogged .. 64 B | logpos 4n | dup n | pclass n]
+    DevBuf in_vok;                // the host form's uploaded value_ok
+    char* host = nullptr;         // pinned image of res
+    size_t host_cap = 0;
+};
+
+__device__ __forceinline__ void copy_row(const LogCols& dst, size_t j, const uint8_t* type, const int64_t* height,
+                                         const int64_t* round, const int64_t* vround, const uint8_t* value32,
+                                         const uint8_t* from32, size_t i) {
+    dst.type[j] = type[i];
+    dst.height[j] = height[i];
+    dst.round[j] = round[i];
+    dst.vround[j] = vround ? vround[i] : -1;
+    const uint4* v = reinterpret_cast<const uint4*>(value32 + 32 * i);
+    const uint4* f = reinterpret_cast<const uint4*>(from32 + 32 * i);
+    uint4* dv = reinterpret_cast<uint4*>(dst.value32 + 32 * j);
+    uint4* df = reinterpret_cast<uint4*>(dst.from32 + 32 * j);
+    const uint4 v0 = v[0], v1 = v[1], f0 = f[0], f1 = f[1];
+    dv[0] = v0;
+    dv[1] = v1;
+    df[0] = f0;
+    df[1] = f1;
+}
+
+__global__ __launch_bounds__(256) void k_log_append(DevBatch b, const uint8_t* __restrict__ verdict,
+                                                    const uint32_t* __restrict__ bitmap,
+                                                    const uint8_t* __restrict__ value_ok, int64_t height, uint32_t L,
+                                                    LogCols lg, uint8_t* __restrict__ vd) {
+    const uint32_t total = L + b.n, stride = gridDim.x * blockDim.x;
+    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < total; q += stride) {
+        if (q < L) {   // retained: its row and value_ok byte are in place
+            vd[q] = V_VALID;
+            continue;
+        }
+        const uint32_t i = q - L;
+        copy_row(lg, q, b.type, b.height, b.round, b.valid_round, b.value32, b.from32, i);
+        lg.vok[q] = value_ok ? (value_ok[i] ? 1 : 0) : 1;
+        bool ok = b.height[i] == height;
+        if (verdict && verdict[i] != V_VALID) ok = false;
+        if (bitmap && !((bitmap[i >> 5] >> (i & 31)) & 1u)) ok = false;
+        vd[q] = ok ? V_VALID : HD_LOG_NOT_CANDIDATE;
+    }
+}
+
+// one block per 256 joined positions, in both passes below
+__global__ __launch_bounds__(256) void k_log_count(uint32_t total, uint32_t L, const uint8_t* __restrict__ dup,
+                                                   const uint8_t* __restrict__ pclass, uint32_t* __restrict__ blk) {
+    __shared__ uint32_t wo[4], wn[4];
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    const bool logged = q < total && (dup[q] == 0 || pclass[q] == 0);
+    const unsigned long long bo = __ballot(logged && q < L), bn = __ballot(logged && q >= L);
+    if ((threadIdx.x & 63) == 0) {
+        wo[threadIdx.x >> 6] = (uint32_t)__popcll(bo);
+        wn[threadIdx.x >> 6] = (uint32_t)__popcll(bn);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        blk[2 * blockIdx.x] = wo[0] + wo[1] + wo[2] + wo[3];
+        blk[2 * blockIdx.x + 1] = wn[0] + wn[1] + wn[2] + wn[3];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_log_keep(uint32_t total, uint32_t L, const uint8_t* __restrict__ dup,
+                                                  const uint8_t* __restrict__ pclass,
+                                                  const uint32_t* __restrict__ blk, LogCols lg, LogCols tmp,
+                                                  uint32_t* __restrict__ hdr, uint32_t* __restrict__ logpos,
+                                                  uint8_t* __restrict__ o_dup, uint8_t* __restrict__ o_pclass) {
+    __shared__ uint32_t part[4], old[4], wn[4];
+    const uint32_t nb = gridDim.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const bool last = blockIdx.x == nb - 1;
+    // kept messages of the blocks before this one; the last block also sums the retained entries
+    // logged again, over every block, for the header
+    uint32_t sn = 0, so = 0;
+    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += 256) sn += blk[2 * k + 1];
+    if (last)
+        for (uint32_t k = threadIdx.x; k < nb; k += 256) so += blk[2 * k];
+    for (int d = 32; d > 0; d >>= 1) {
+        sn += (uint32_t)__shfl_xor((int)sn, d, 64);
+        so += (uint32_t)__shfl_xor((int)so, d, 64);
+    }
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    const bool fresh = q < total && q >= L;
+    const uint8_t du = fresh ? dup[q] : 3, pc = fresh ? pclass[q] : 3;
+    const bool keep = fresh && (du == 0 || pc == 0);
+    const unsigned long long bal = __ballot(keep);
+    if (lane == 0) {
+        part[w] = sn;
+        old[w] = so;
+        wn[w] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    uint32_t off = part[0] + part[1] + part[2] + part[3];
+    if (last && threadIdx.x == 0) {
+        hdr[0] = off + wn[0] + wn[1] + wn[2] + wn[3];   // kept
+        hdr[1] = old[0] + old[1] + old[2] + old[3];     // relogged
+    }
+    if (!fresh) return;
+    for (uint32_t k = 0; k < w; k++) off += wn[k];
+    const uint32_t j = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+    const uint32_t i = q - L;
+    o_dup[i] = du;
+    o_pclass[i] = pc;
+    logpos[i] = keep ? L + j : HD_WHEN_NEVER;
+    if (keep) {   // j < the batch's size: tmp has a row for every new message
+        copy_row(tmp, j, lg.type, lg.height, lg.round, lg.vround, lg.value32, lg.from32, q);
+        tmp.vok[j] = lg.vok[q];
+    }
+}
+
+// the accepted insert's kept rows, from the second buffer to their place behind the retained entries
+__global__ __launch_bounds__(256) void k_log_commit(uint32_t kept, uint32_t L, LogCols tmp, LogCols lg) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < kept; j += stride) {
+        copy_row(lg, (size_t)L + j, tmp.type, tmp.height, tmp.round, tmp.vround, tmp.value32, tmp.from32, j);
+        lg.vok[(size_t)L + j] = tmp.vok[j];
+    }
+}
+
+// ---------------------------------------------------------------- host side
+#define LCHK(expr, what)                                         \
+    do {                                                         \
+        hipError_t _e = (expr);                                  \
+        if (_e != hipSuccess) return hd_ctx_fail(ctx, _e, what); \
+    } while (0)
+
+static void cols_free(LogCols& c) {
+    for (int k = 0; k < 7; k++) {
+        void** p = log_col(c, k);
+        if (*p) (void)hipFree(*p);
+        *p = nullptr;
+    }
+}
+
+// rows for `need` items; the first `keep` rows survive a regrow (copied on s)
+static int cols_grow(hd_ctx* ctx, LogCols& c, size_t& cap, size_t need, size_t keep, hipStream_t s) {
+    if (need <= cap) return HD_OK;
+    const size_t want = std::max(need + need / 4, (size_t)4096);
+    LogCols nw{};
+    for (int k = 0; k < 7; k++) {
+        hipError_t e = hipMalloc(log_col(nw, k), kLogWidth[k] * want);
+        if (e != hipSuccess) {
+            cols_free(nw);
+            return hd_ctx_fail(ctx, e, "log hipMalloc");
+        }
+    }
+    if (keep) {
+        hipError_t e = hipSuccess;
+        for (int k = 0; k < 7 && e == hipSuccess; k++)
+            e = hipMemcpyAsync(*log_col(nw, k), *log_col(c, k), kLogWidth[k] * keep, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            cols_free(nw);
+            return hd_ctx_fail(ctx, e, "log regrow copy");
+        }
+    }
+    cols_free(c);
+    c = nw;
+    cap = want;
+    return HD_OK;
+}
+
+static int buf_grow(hd_ctx* ctx, DevBuf& b, size_t need) { return hd_dev_grow(ctx, &b.p, &b.cap, need); }
+
+static size_t log_pad(size_t n) { return (n + 63) & ~(size_t)63; }
+
+struct KeepArgs {
+    hd_log* lg;
+    uint32_t n, total, nb;
+    size_t res_bytes;
+};
+
+// hd_decide_run's hook: dup / pclass are complete on the stream
+static int log_queue_keep(void* arg, hipStream_t s) {
+    const KeepArgs* a = static_cast<const KeepArgs*>(arg);
+    hd_log* lg = a->lg;
+    hd_ctx* ctx = lg->ctx;
+    char* res = (char*)lg->res.p;
+    const uint8_t *dup = (const uint8_t*)lg->dup.p, *pclass = (const uint8_t*)lg->pclass.p;
+    uint32_t* blk = (uint32_t*)lg->blk.p;
+    const size_t lp_off = 64, dup_off = lp_off + log_pad(4 * (size_t)a->n), pc_off = dup_off + log_pad(a->n);
+    k_log_count<<<a->nb, 256, 0, s>>>(a->total, lg->L, dup, pclass, blk);
+    k_log_keep<<<a->nb, 256, 0, s>>>(a->total, lg->L, dup, pclass, blk, lg->lg, lg->tmp, (uint32_t*)res,
+                                     (uint32_t*)(res + lp_off), (uint8_t*)(res + dup_off), (uint8_t*)(res + pc_off));
+    LCHK(hipGetLastError(), "log keep kernels");
+    LCHK(hipMemcpyAsync(lg->host, res, a->res_bytes, hipMemcpyDeviceToHost, s), "log download");
+    return HD_OK;
+}
+
+static bool log_out_ok(const hd_decide_out* o, const hd_decide_order* w) {
+    return o && o->height && o->round && o->rep && o->propose && o->prevotes && o->precommits && o->trace &&
+           o->pv_value && o->pc_value && o->pv_nil && o->pv_validround && o->flags && o->bits && w && w->when &&
+           w->exact_until && w->cap >= o->cap;
+}
+
+// db, d_verdict / d_bitmap (one of them) and d_vok are device pointers
+static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, const uint32_t* d_bitmap,
+                      const uint8_t* d_vok, hd_decide_out* out, hd_decide_order* order, hd_log_info* info,
+                      hipStream_t s) {
+    hd_ctx* ctx = lg->ctx;
+    const uint32_t n = db->n, L = lg->L, total = L + n;
+    if (total == 0) return HD_OK;
+    const uint32_t nb = (total + 255u) / 256u;
+    int rc = cols_grow(ctx, lg->lg, lg->cap_items, total, L, s);
+    if (!rc) rc = cols_grow(ctx, lg->tmp, lg->cap_new, std::max(n, 1u), 0, s);
+    if (!rc) rc = buf_grow(ctx, lg->vd, total);
+    if (!rc) rc = buf_grow(ctx, lg->dup, total);
+    if (!rc) rc = buf_grow(ctx, lg->pclass, total);
+    if (!rc) rc = buf_grow(ctx, lg->blk, 8 * (size_t)nb);
+    const size_t res_bytes = 64 + log_pad(4 * (size_t)n) + 2 * log_pad(n);
+    if (!rc) rc = buf_grow(ctx, lg->res, res_bytes);
+    if (rc) return rc;
+    if (lg->host_cap < res_bytes) {
+        if (lg->host) (void)hipHostFree(lg->host);
+        lg->host = nullptr;
+        lg->host_cap = 0;
+        LCHK(hipHostMalloc((void**)&lg->host, res_bytes + (res_bytes >> 2), hipHostMallocDefault), "log host stage");
+        lg->host_cap = res_bytes + (res_bytes >> 2);
+    }
+    DevBatch b{n, db->type, db->height, db->round, db->valid_round, db->value32, db->from32, nullptr};
+    const uint32_t grid = std::min<uint32_t>(nb, (uint32_t)ctx->n_cu * 16u);
+    k_log_append<<<grid, 256, 0, s>>>(b, d_verdict, d_bitmap, d_vok, lg->height, L, lg->lg, (uint8_t*)lg->vd.p);
+    LCHK(hipGetLastError(), "log append");
+    hd_batch jb;
+    jb.n = total;
+    jb.type = lg->lg.type;
+    jb.height = lg->lg.height;
+    jb.round = lg->lg.round;
+    jb.valid_round = lg->lg.vround;
+    jb.value32 = lg->lg.value32;
+    jb.from32 = lg->lg.from32;
+    jb.sig65 = nullptr;
+    KeepArgs ka{lg, n, total, nb, res_bytes};
+    const DecideExt ext{(uint8_t*)lg->dup.p, (uint8_t*)lg->pclass.p, log_queue_keep, &ka};
+    rc = hd_decide_run(ctx, &jb, (const uint8_t*)lg->vd.p, nullptr,
+                       DecideIn{lg->f, lg->n_sched, lg->n_sched ? lg->d_sched : nullptr, lg->lg.vok}, out, s, order,
+                       &ext);
+    (void)hd_ctx_note_stream(ctx, s);
+    if (rc) return rc;
+    const uint32_t* hdr = reinterpret_cast<const uint32_t*>(lg->host);
+    const uint32_t kept = hdr[0], relogged = hdr[1];
+    info->kept = kept;
+    info->relogged = relogged;
+    if (relogged != L || kept > n) {
+        ctx->last_error = "hd_log: the replay did not log every retained entry again";
+        return HD_EDEVICE;
+    }
+    if (lg->max_entries && (uint64_t)L + kept > lg->max_entries) return HD_ECAP;
+    const size_t lp_off = 64, dup_off = lp_off + log_pad(4 * (size_t)n), pc_off = dup_off + log_pad(n);
+    if (info->logpos) memcpy(info->logpos, lg->host + lp_off, 4 * (size_t)n);
+    if (out->dup) memcpy(out->dup, lg->host + dup_off, n);
+    if (out->pclass) memcpy(out->pclass, lg->host + pc_off, n);
+    if (kept) {   // the kept rows behind the retained ones; ordered before the next call by the stream
+        k_log_commit<<<std::min<uint32_t>((kept + 255u) / 256u, (uint32_t)ctx->n_cu * 16u), 256, 0, s>>>(
+            kept, L, lg->tmp, lg->lg);
+        LCHK(hipGetLastError(), "log commit");
+        (void)hd_ctx_note_stream(ctx, s);
+    }
+    lg->L = L + kept;
+    return HD_OK;
+}
+
+static bool log_args_ok(const hd_log* lg, const hd_batch* b, const hd_decide_out* out, const hd_decide_order* order,
+                        hd_log_info* info) {
+    if (!lg || !lg->ctx || !b || !info || !log_out_ok(out, order)) return false;
+    if (b->n && (!b->type || !b->height || !b->round || !b->value32 || !b->from32)) return false;
+    return (uint64_t)lg->L + b->n < (1ull << 30);
+}
+
+extern "C" {
+
+int hd_log_create(hd_ctx* ctx, hd_log** out) {
+    if (!ctx || !out) return HD_EINVAL;
+    hd_log* lg = new (std::nothrow) hd_log();
+    if (!lg) return HD_ENOMEM;
+    lg->ctx = ctx;
+    lg->device = ctx->device;
+    *out = lg;
+    return HD_OK;
+}
+
+int hd_log_destroy(hd_log* lg) {
+    if (!lg) return HD_EINVAL;
+    (void)hipSetDevice(lg->device);
+    (void)hipDeviceSynchronize();   // a commit's copies may still be queued on a caller's stream
+    cols_free(lg->lg);
+    cols_free(lg->tmp);
+    DevBuf* bufs[] = {&lg->vd, &lg->dup, &lg->pclass, &lg->blk, &lg->res, &lg->in_vok};
+    for (DevBuf* b : bufs)
+        if (b->p) (void)hipFree(b->p);
+    if (lg->d_sched) (void)hipFree(lg->d_sched);
+    if (lg->host) (void)hipHostFree(lg->host);
+    delete lg;
+    return HD_OK;
+}
+
+int hd_log_reset(hd_log* lg, int64_t height, uint32_t f, const uint8_t* sched32, uint32_t n_sched,
+                 uint32_t max_entries) {
+    if (!lg || !lg->ctx || (sched32 && n_sched == 0)) return HD_EINVAL;
+    hd_ctx* ctx = lg->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (sched32) {
+        // an earlier insert's kernels may still read the old schedule on the context's stream
+        LCHK(hipStreamSynchronize(ctx->stream), "log reset sync");
+        int rc = hd_dev_grow(ctx, (void**)&lg->d_sched, &lg->cap_sched, 32 * (size_t)n_sched);
+        if (rc) return rc;
+        LCHK(hipMemcpy(lg->d_sched, sched32, 32 * (size_t)n_sched, hipMemcpyHostToDevice), "log schedule upload");
+    }
+    lg->n_sched = sched32 ? n_sched : 0;
+    lg->height = height;
+    lg->f = f;
+    lg->max_entries = max_entries;
+    lg->L = 0;
+    return HD_OK;
+}
+
+int hd_log_len(const hd_log* lg, int64_t* height, uint32_t* entries) {
+    if (!lg) return HD_EINVAL;
+    if (height) *height = lg->height;
+    if (entries) *entries = lg->L;
+    return HD_OK;
+}
+
+int hd_log_insert(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
+                  hd_decide_out* out, hd_decide_order* order, hd_log_info* info) {
+    if (!log_args_ok(lg, batch, out, order, info) || (batch->n && !verdict)) return HD_EINVAL;
+    hd_ctx* ctx = lg->ctx;
+    out->n = 0;
+    info->base = lg->L;
+    info->kept = info->relogged = 0;
+    const uint32_t n = batch->n;
+    (void)hipSetDevice(ctx->device);
+    hd_batch db;
+    memset(&db, 0, sizeof db);
+    const uint8_t *d_v = nullptr, *d_vok = nullptr;
+    if (n) {
+        hd_batch hb = *batch;
+        hb.sig65 = nullptr;   // not kept: Equal ignores it
+        int rc = hd_upload_batch(ctx, &hb, &db);
+        if (!rc) rc = hd_dev_grow(ctx, &ctx->bufs[BUF_VERDICT].p, &ctx->bufs[BUF_VERDICT].cap, n);
+        if (!rc && value_ok) rc = buf_grow(ctx, lg->in_vok, n);
+        if (rc) return rc;
+        LCHK(hipMemcpyAsync(ctx->bufs[BUF_VERDICT].p, verdict, n, hipMemcpyHostToDevice, ctx->stream),
+             "verdict upload");
+        d_v = (const uint8_t*)ctx->bufs[BUF_VERDICT].p;
+        if (value_ok) {
+            LCHK(hipMemcpyAsync(lg->in_vok.p, value_ok, n, hipMemcpyHostToDevice, ctx->stream), "value_ok upload");
+            d_vok = (const uint8_t*)lg->in_vok.p;
+        }
+    }
+    return log_insert(lg, &db, d_v, nullptr, d_vok, out, order, info, ctx->stream);
+}
+
+int hd_log_insert_device_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
+                                hd_log_info* info, void* stream) {
+    if (!log_args_ok(lg, dbatch, out, order, info) || (dbatch->n && !d_valid_bitmap)) return HD_EINVAL;
+    hd_ctx* ctx = lg->ctx;
+    out->n = 0;
+    info->base = lg->L;
+    info->kept = info->relogged = 0;
+    (void)hipSetDevice(ctx->device);
+    return log_insert(lg, dbatch, nullptr, dbatch->n ? d_valid_bitmap : nullptr, d_value_ok, out, order, info,
+                      stream ? (hipStream_t)stream : ctx->stream);
+}
+
+}  // extern "C"

@@ -1570,11 +1570,7 @@ HD_HOSTONLY DecideCols decide_cols(char* base, uint32_t cap) {
     return x;
 }
 
-struct DecideIn {
-    uint32_t f, n_sched;
-    const uint8_t* sched32;    // device
-    const uint8_t* value_ok;   // device
-};
+// DecideIn (f, the device schedule and value_ok): hd_internal.h
 
 __device__ __forceinline__ bool msg_valid(const uint8_t* verdict, const uint32_t* bitmap, uint32_t i) {
     if (verdict && verdict[i] != V_VALID) return false;
@@ -2096,9 +2092,10 @@ static void decide_unpack(const DecideCols& x, uint32_t rows, uint32_t at, hd_de
 // capacity H]; rows past H come from the overflow columns by a second round
 // of copies.  With `ord` (hd_decide_ordered) the stage continues with
 // [when (8 words per row) | exact_until] at capacity H, and the overflow
-// buffer likewise after its rows.
-static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap,
-                         DecideIn in, hd_decide_out* out, hipStream_t s, hd_decide_order* ord = nullptr) {
+// buffer likewise after its rows.  With `ext` (hd_log.hip) the classes go to
+// the caller's device arrays instead of the stage (hd_internal.h).
+int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap, DecideIn in,
+                  hd_decide_out* out, hipStream_t s, hd_decide_order* ord, const DecideExt* ext) {
     const uint32_t n = hb->n, m = n;
     if (!ctx->tally) ctx->tally = new TallyWork();
     TallyWork* tw = ctx->tally;
@@ -2106,14 +2103,15 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
     static const uint32_t bpc = getenv("HD_TALLY_BPC") ? (uint32_t)std::max(1, atoi(getenv("HD_TALLY_BPC"))) : 16u;
     int rc = 0;
     const uint32_t H = tw->guess_dec;
-    const size_t dup_off = 64, pc_off = dup_off + (out->dup ? decide_pad(n) : 0),
-                 rows_off = pc_off + (out->pclass ? decide_pad(n) : 0);
+    const bool st_dup = !ext && out->dup, st_pclass = !ext && out->pclass;   // staged and downloaded
+    const size_t dup_off = 64, pc_off = dup_off + (st_dup ? decide_pad(n) : 0),
+                 rows_off = pc_off + (st_pclass ? decide_pad(n) : 0);
     const size_t when_off = rows_off + decide_pad(HD_DECIDE_ROW_BYTES * (size_t)H), until_off = when_off + 32 * (size_t)H;
     const size_t total = ord ? until_off + 4 * (size_t)H + 64 : rows_off + HD_DECIDE_ROW_BYTES * (size_t)H + 64;
     char* st = (char*)tbuf(ctx, T_DSTAGE, total, &rc);
     if (rc) return rc;
-    uint8_t* d_dup = out->dup ? (uint8_t*)(st + dup_off) : nullptr;
-    uint8_t* d_pclass = out->pclass ? (uint8_t*)(st + pc_off) : nullptr;
+    uint8_t* d_dup = ext ? ext->d_dup : st_dup ? (uint8_t*)(st + dup_off) : nullptr;
+    uint8_t* d_pclass = ext ? ext->d_pclass : st_pclass ? (uint8_t*)(st + pc_off) : nullptr;
     const uint32_t grid = std::min<uint32_t>(nblk(m), (uint32_t)ctx->n_cu * bpc);
     uint32_t cap = 1024;
     while (cap < 2 * m) cap <<= 1;
@@ -2209,6 +2207,10 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
     k_decide_clean<<<grid, 256, 0, s>>>(m, gslot, cslot, ref, pslot, G, C, d, P, Bg, ctr);
     TCHK(hipGetLastError(), "decide order kernels");
     tw->dirty = tw->pdirty = false;
+    if (ext && ext->queued) {
+        rc = ext->queued(ext->arg, s);
+        if (rc) return rc;
+    }
     if (tw->host_cap < total) {
         if (tw->host) (void)hipHostFree(tw->host);
         tw->host = nullptr;
@@ -2223,8 +2225,8 @@ static int decide_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdi
     out->n = rows;
     tw->guess_dec = std::max<uint32_t>(1024u, rows + rows / 4);
     if (rows > out->cap) return HD_ECAP;
-    if (out->dup) memcpy(out->dup, hs + dup_off, n);
-    if (out->pclass) memcpy(out->pclass, hs + pc_off, n);
+    if (st_dup) memcpy(out->dup, hs + dup_off, n);
+    if (st_pclass) memcpy(out->pclass, hs + pc_off, n);
     decide_unpack(decide_cols(const_cast<char*>(hs) + rows_off, H), std::min(rows, H), 0, out);
     if (ord) {
         memcpy(ord->when, hs + when_off, 32 * (size_t)std::min(rows, H));
@@ -2291,7 +2293,7 @@ static int decide_host(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdic
         TCHK(hipMemcpyAsync(p, in->value_ok, n, hipMemcpyHostToDevice, ctx->stream), "value_ok upload");
         di.value_ok = p;
     }
-    return decide_device(ctx, &db, d_v, nullptr, di, out, ctx->stream, ord);
+    return hd_decide_run(ctx, &db, d_v, nullptr, di, out, ctx->stream, ord, nullptr);
 }
 
 static int decide_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap, const hd_decide_in* in,
@@ -2304,8 +2306,8 @@ static int decide_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_
     out->n = 0;
     if (dbatch->n == 0) return HD_OK;
     (void)hipSetDevice(ctx->device);
-    return decide_device(ctx, dbatch, nullptr, d_valid_bitmap, DecideIn{in->f, in->n_sched, in->sched32, in->value_ok},
-                         out, stream ? (hipStream_t)stream : ctx->stream, ord);
+    return hd_decide_run(ctx, dbatch, nullptr, d_valid_bitmap, DecideIn{in->f, in->n_sched, in->sched32, in->value_ok},
+                         out, stream ? (hipStream_t)stream : ctx->stream, ord, nullptr);
 }
 
 extern "C" {

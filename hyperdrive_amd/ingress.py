@@ -14,6 +14,8 @@ for a whole batch:
     res = ing.flush()                       # mq.Consume(h, procsAllowed) + vote-log inserts (host table)
     res.proposes                            # handed to the CPU's insertPropose (scheduler/validator)
     res.events                              # HD_VOTE_EV_* quorum crossings per delivered vote (f known)
+    ing.open_log(schedule)                  # a device log of the height (hd_log): proposes included
+    res, dec = ing.flush_decide()           # flush() + the rules the consumed messages fired (dec.new_firings)
     ing.advance_height(h + 1)               # the Process committed: CurrentHeight++, logs emptied (process.go:710-725)
     ing.reset_height(h + 5, signatories)    # ResetHeight: ignored unless above the current height
                                             # (replica.go:222-225); logs emptied, mq.DropMessagesBelowHeight,
@@ -100,12 +102,16 @@ class Ingress:
         # no insert since, every message in it is above that height, so a
         # ResetHeight to at most height + 1 has nothing to drop
         self._clean = None
+        self.log = None   # open_log: the height's device log (hd_log), fed by flush_decide
 
     def _set_f(self, f: int) -> None:
         self.f = int(f)
         self.votes.set_f(self.f)
 
     def close(self):
+        if self.log is not None:
+            self.log.close()
+            self.log = None
         self.mq.close()
         self.votes.close()
 
@@ -223,6 +229,31 @@ class Ingress:
         self._clean = (self.height, mq.inserts)
         return FlushResult(b, senders, status, double_of, None, mq.last_removed, events)
 
+    def open_log(self, schedule=None):
+        """Open a DecideLog (hd_log) at the ingress's height and f: the propose
+        log and every quorum rule of the height, kept on the device from flush
+        to flush.  schedule: the round-robin order for the turn check (None:
+        no turn check).  Returns the log (also ``self.log``)."""
+        if self.log is not None:
+            self.log.close()
+        self.log = self.v.open_log(self.height, self.f or 0, schedule)
+        return self.log
+
+    def flush_decide(self, value_ok=None):
+        """flush() followed by one insert of the consumed batch into the open
+        log.  Every consumed message is authenticated and admitted, so its
+        verdict is VALID.  value_ok stands in for validator.Valid on the
+        proposes' values: None (every non-nil value is valid), one byte per
+        consumed message, or -- the consumed batch is not known before the
+        flush -- a callable that takes the consumed Batch and returns those
+        bytes.  Returns (FlushResult, LogInsertResult)."""
+        if self.log is None:
+            raise RuntimeError("flush_decide without open_log")
+        res = self.flush()
+        b = res.consumed
+        vok = value_ok(b) if callable(value_ok) else value_ok
+        return res, self.log.insert(b, np.zeros(len(b), np.uint8), vok)
+
     def advance_height(self, height: int) -> None:
         """The Process's own height change after a commit (process.go:710-725:
         CurrentHeight = height, vote logs emptied); the queue keeps its
@@ -232,6 +263,8 @@ class Ingress:
             raise ValueError(f"advance_height({height}) at height {self.height}")
         self.height = int(height)
         self.votes.reset(self.height)
+        if self.log is not None:
+            self.log.reset(self.height)
 
     def reset_height(self, height: int, signatories=None) -> bool:
         """Replica.ResetHeight (replica.go:216-235): ignored (returns False)
@@ -249,6 +282,8 @@ class Ingress:
         if signatories is not None and len(signatories):
             self.v.set_signatories(signatories)
             self._set_f(len(signatories) // 3)
+        if self.log is not None:
+            self.log.reset(self.height, self.f or 0)
         return True
 
 

@@ -235,6 +235,147 @@ class OrderedDecideResult(DecideResult):
         return [(i, h, r, DECISION_KEYS[k]) for i, k, h, r in out]
 
 
+@dataclass
+class LogInsertResult(OrderedDecideResult):
+    """One :meth:`DecideLog.insert`: the OrderedDecideResult of the whole
+    stream so far, in joined coordinates -- an index below ``base`` is a log
+    position (an earlier insert's ``logpos``), an index at or above it is
+    message ``index - base`` of this batch.  pclass / dup / logpos have one
+    entry per message of this batch."""
+    base: int = 0                    # entries before this insert
+    kept: int = 0                    # entries this insert added
+    logpos: np.ndarray = None        # uint32[n]: the message's log position, WHEN_NEVER when it was not kept
+    relogged: int = 0                # retained entries the replay logged again: always == base
+
+    @property
+    def new_firings(self) -> List[Tuple[int, int, int, str]]:
+        """The firings of this insert: (index into this batch, height, round,
+        name) of every predicate that first held at one of its messages."""
+        return [(i - self.base, h, r, k) for i, h, r, k in self.firings if i >= self.base]
+
+
+class DecideLog:
+    """A height's vote and propose logs kept on the device across inserts
+    (include/hd_log.h): every insert returns what decide_ordered would return
+    for all the batches inserted since the last reset, joined."""
+
+    def __init__(self, v: "Verifier", height: int, f: int, schedule=None, max_entries: int = 0):
+        self._v = v
+        self._lib = v._lib
+        h = ctypes.c_void_p()
+        v._check(self._lib.hd_log_create(v.handle, ctypes.byref(h)), "hd_log_create")
+        self._log = h
+        self._close_rank = 0          # closed before its Verifier
+        _lib.track(self)
+        self.max_entries = int(max_entries)
+        self.f = int(f)
+        self._sched = None
+        self._rows = 0                # rows of the last insert: the next has at most this many more than its batch
+        self.reset(height, f, schedule)
+
+    def close(self):
+        if getattr(self, "_log", None):
+            self._lib.hd_log_destroy(self._log)
+            self._log = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._log
+
+    def reset(self, height: int, f: Optional[int] = None, schedule=None) -> None:
+        """Empties the log and sets its height; f and schedule: None keeps the
+        current one."""
+        if f is not None:
+            self.f = int(f)
+        if schedule is not None:
+            sched = _as_rows(schedule, 32)
+            if len(sched) == 0:
+                raise ValueError("an empty schedule (pass None for no turn check)")
+            self._sched = sched
+        s = self._sched
+        self._v._check(self._lib.hd_log_reset(self._log, int(height), self.f, _ptr(s), len(s) if s is not None else 0,
+                                              self.max_entries), "hd_log_reset")
+        self._rows = 0
+
+    def _len(self) -> Tuple[int, int]:
+        h, e = ctypes.c_int64(), ctypes.c_uint32()
+        self._v._check(self._lib.hd_log_len(self._log, ctypes.byref(h), ctypes.byref(e)), "hd_log_len")
+        return h.value, e.value
+
+    @property
+    def height(self) -> int:
+        return self._len()[0]
+
+    @property
+    def entries(self) -> int:
+        return self._len()[1]
+
+    def _outputs(self, n: int):
+        from ._lib import HdLogInfo
+        cap = self._rows + n
+        o, a = Verifier._decide_struct(n, cap)
+        w, when, until = Verifier._order_struct(cap)
+        logpos = np.full(max(n, 1), WHEN_NEVER, np.uint32)
+        info = HdLogInfo(0, 0, 0, _ptr(logpos))
+        return o, a, w, when, until, logpos, info
+
+    def _result(self, n, o, a, when, until, logpos, info) -> LogInsertResult:
+        self._rows = o.n
+        rows = {k: a[k][: o.n].copy() for k in type(o).ROW_FIELDS}
+        return LogInsertResult(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), when=when[: o.n].copy(),
+                               exact_until=until[: o.n].copy(), base=info.base, kept=info.kept,
+                               logpos=logpos[:n].copy(), relogged=info.relogged, **rows)
+
+    def insert(self, batch: Batch, verdict: np.ndarray, value_ok=None) -> LogInsertResult:
+        """hd_log_insert of a host batch with its verdicts (and value_ok, one
+        byte per message, as :meth:`Verifier.decide`)."""
+        n = len(batch)
+        verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
+        if len(verdict) != n:
+            raise ValueError("verdict length mismatch")
+        vok = np.ascontiguousarray(value_ok, dtype=np.uint8) if value_ok is not None else None
+        if vok is not None and len(vok) != n:
+            raise ValueError("value_ok length mismatch")
+        o, a, w, when, until, logpos, info = self._outputs(n)
+        cb = batch.c_struct()
+        self._v._check(self._lib.hd_log_insert(self._log, ctypes.byref(cb), _ptr(verdict), _ptr(vok), ctypes.byref(o),
+                                               ctypes.byref(w), ctypes.byref(info)), "hd_log_insert")
+        return self._result(n, o, a, when, until, logpos, info)
+
+    def insert_device(self, dbatch: HdBatch, d_bitmap: int, value_ok=None,
+                      stream: Optional[int] = None) -> LogInsertResult:
+        """hd_log_insert_device_bitmap over a device batch and the valid bitmap
+        of verify_batch_device (bit i is message i of `dbatch`).  value_ok: a
+        torch uint8 tensor on the device, or a host array, which is uploaded
+        first."""
+        import torch
+        n = dbatch.n
+        vok = value_ok
+        if vok is not None and not isinstance(vok, torch.Tensor):
+            vok = torch.from_numpy(np.ascontiguousarray(vok, dtype=np.uint8)).cuda()
+            torch.cuda.current_stream().synchronize()
+        if vok is not None and vok.numel() != n:
+            raise ValueError("value_ok length mismatch")
+        o, a, w, when, until, logpos, info = self._outputs(n)
+        self._v._check(self._lib.hd_log_insert_device_bitmap(self._log, ctypes.byref(dbatch), d_bitmap,
+                                                             vok.data_ptr() if vok is not None else None,
+                                                             ctypes.byref(o), ctypes.byref(w), ctypes.byref(info),
+                                                             stream), "hd_log_insert_device_bitmap")
+        return self._result(n, o, a, when, until, logpos, info)
+
+
 class Verifier:
     """One context per caller thread (the reference's Process is
     single-goroutine, process/process.go:100-101)."""
@@ -619,6 +760,16 @@ class Verifier:
                                                               ctypes.byref(cin), ctypes.byref(o), ctypes.byref(w),
                                                               stream), "hd_decide_ordered_device_bitmap")
         return self._ordered_result(n, o, a, when, until)
+
+    # ---- decide across calls -----------------------------------------
+    def open_log(self, height: int, f: int, schedule=None, max_entries: int = 0) -> DecideLog:
+        """A device-resident log of one height on this context (hd_log):
+        ``log.insert(batch, verdict)`` after ``log.insert(...)`` returns what
+        :meth:`decide_ordered` would return for the batches joined.
+        max_entries: the most entries the log may hold (0: no limit).  The
+        log's inserts and this verifier's tallies and decides go on one
+        stream."""
+        return DecideLog(self, height, f, schedule, max_entries)
 
     # ---- synthetic workload ------------------------------------------
     def gen_keys(self, S: int) -> Tuple[np.ndarray, np.ndarray]:

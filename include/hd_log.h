@@ -1,0 +1,87 @@
+/* hd_log.h -- a height's vote and propose logs kept on the device across
+ * decide calls.
+ *
+ * hd_decide_ordered answers "which quorum rules hold and at which message did
+ * each fire" for one batch in isolation.  The reference's Process keeps its
+ * ProposeLogs / PrevoteLogs / PrecommitLogs / TraceLogs from insert to insert
+ * and empties them only when the height changes (process/process.go:710-725);
+ * a height's messages arrive over many flushes.  An hd_log is that state for
+ * one height: it accepts batch after batch and after each one returns exactly
+ * what hd_decide_ordered would return for the whole stream so far.
+ *
+ * The log retains, in arrival order, every message the reference would have
+ * in its logs: each logged vote (dup == 0) and each logged propose
+ * (pclass == 0), with the fields decide reads (type, height, round,
+ * valid_round, value, From, value_ok; no signature -- Equal ignores it).  An
+ * entry's position never changes while the height lasts.  An insert replays
+ * [retained entries | batch] through the ordered decide passes: first-wins is
+ * "lowest index", every retained entry is the only one of its key and lies
+ * below every new message, so each is logged again and the outcome is the
+ * one-shot outcome of the whole stream.
+ *
+ * Indices (rep, propose, when, exact_until) are in joined coordinates: a value
+ * below `base` (the entries before the call) is a log position, which the
+ * caller has seen in an earlier call's logpos; a value >= base is message
+ * (value - base) of this batch.  A rule fired in this call exactly when its
+ * `when` is >= base.  Rows are reported for every round of the height that has
+ * anything logged, in the order of each round's first logged item.
+ *
+ * A log uses its context's tally scratch: its calls and the context's
+ * tallies and decides go on one stream (the rule for tallies).  A set change
+ * on the context between inserts is allowed and changes no output. */
+#ifndef HD_LOG_H
+#define HD_LOG_H
+
+#include "hd_verify.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct hd_log hd_log;
+
+int hd_log_create(hd_ctx* ctx, hd_log** out);
+/* the context may be destroyed before or after its logs */
+int hd_log_destroy(hd_log* log);
+/* Empties the log and sets the height, f (the thresholds are 2f+1 and f+1),
+ * the round-robin schedule (n_sched x 32 bytes, copied to the device; NULL: no
+ * turn check) and the most entries the log may hold (0: no limit).  A new log
+ * is at height 0 with f = 0 and no schedule. */
+int hd_log_reset(hd_log* log, int64_t height, uint32_t f, const uint8_t* sched32, uint32_t n_sched,
+                 uint32_t max_entries);
+/* either output may be NULL */
+int hd_log_len(const hd_log* log, int64_t* height, uint32_t* entries);
+
+typedef struct {
+    uint32_t base;      /* entries before this insert */
+    uint32_t kept;      /* entries this insert added  */
+    uint32_t relogged;  /* retained entries logged again by the replay: must equal base */
+    uint32_t* logpos;   /* n words or NULL: each message's log position, or HD_WHEN_NEVER */
+} hd_log_info;
+
+/* One insert.  A message is a candidate when its verdict is VALID and its
+ * height is the log's; any other message comes out as dup 3 / pclass 3 (the
+ * reference's inserts reject another height first, process.go:759, 824, 861).
+ * out->pclass and out->dup (each optional) have n entries, for this batch's
+ * messages only; out->cap and order->cap count rows (order->cap >= out->cap).
+ * A batch of n = 0 reports the log as it stands (zero rows on an empty log).
+ *
+ * HD_EINVAL for NULL arguments or base + n >= 2^30, before any device work;
+ * HD_ECAP with out->n set when out->cap is too small; HD_ECAP with info->kept
+ * set when the insert would exceed max_entries; HD_EDEVICE when relogged !=
+ * base.  Any error leaves the log as it was before the call.
+ *
+ * Host buffers; value_ok n bytes or NULL. */
+int hd_log_insert(hd_log* log, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
+                  hd_decide_out* out, hd_decide_order* order, hd_log_info* info);
+/* Device batch, valid bitmap (hd_verify_batch_device's; bit i is message i of
+ * this batch) and value_ok; host outputs; synchronises `stream` (NULL: the
+ * context's). */
+int hd_log_insert_device_bitmap(hd_log* log, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
+                                hd_log_info* info, void* stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif

@@ -31,6 +31,8 @@
  *                       holds when the batch is inserted one message at a
  *                       time (the rules are tried after every insert,
  *                       process.go:229-269).
+ *   hd_log (hd_log.h)   the same across calls: a height's logs kept on the
+ *                       device until the height changes (process.go:710-725).
  *
  * Ownership: all host buffers are caller-owned; the library copies what it
  * needs and keeps no pointer after a call returns.  Device buffers passed to
