@@ -75,21 +75,87 @@ HD void dd_key_load(DdKey& k, const int64_t* height, const int64_t* round, const
 // (signature bytes 0-3, 28-31, 32-35, 60-63; From bytes 0-3, 28-31) and
 // nothing else: r alone would let one signature's R collide every message
 // that reuses it, and From spreads one replayed signature over senders.
-HD uint32_t dd_hash(const DdKey& k) {
-    uint32_t h = k.r[0] * 0x9E3779B1u;
-    h = (h ^ k.r[7]) * 0x85EBCA6Bu;
-    h = (h ^ (h >> 15) ^ k.s[0]) * 0xC2B2AE35u;
-    h = (h ^ k.s[7]) * 0x27D4EB2Fu;
-    h = (h ^ (h >> 13) ^ k.from[0]) * 0x165667B1u;
-    h = (h ^ k.from[7]) * 0x9E3779B1u;
+HD uint32_t dd_hash_words(uint32_t r0, uint32_t r7, uint32_t s0, uint32_t s7, uint32_t f0, uint32_t f7) {
+    uint32_t h = r0 * 0x9E3779B1u;
+    h = (h ^ r7) * 0x85EBCA6Bu;
+    h = (h ^ (h >> 15) ^ s0) * 0xC2B2AE35u;
+    h = (h ^ s7) * 0x27D4EB2Fu;
+    h = (h ^ (h >> 13) ^ f0) * 0x165667B1u;
+    h = (h ^ f7) * 0x9E3779B1u;
     return h ^ (h >> 16);
 }
+HD uint32_t dd_hash(const DdKey& k) { return dd_hash_words(k.r[0], k.r[7], k.s[0], k.s[7], k.from[0], k.from[7]); }
 
 // Table words for a batch of n: a power of two >= 4 n (load <= 1/4), >= 1024.
 HD uint32_t dd_table_words(uint32_t n) {
     uint32_t w = 1024u;
     while (w < 4u * (uint64_t)n && w < 0x80000000u) w <<= 1;
     return w;
+}
+
+// ---- shared preimages (k_pre_claim / k_pre_hash; DESIGN.md §4 "preimages") --
+// The digest of a message is SHA-256 over (height, round, value) for a vote
+// and over (height, round, valid_round, value) for a propose: no type beyond
+// that, no sender.  Every signatory of a round signs the same preimage, so a
+// call hashes each distinct preimage once.  A second table of message indices
+// (same scheme as above: one compare-and-swap on the first free slot of
+// HD_DD_PROBES, a full compare on a claimed slot, its own claimant past the
+// cutoff) gives every typed message a preimage id.
+// pid[i], the per-message word k_fast_prep resolves a digest row through:
+//   < 2^30              the message's own preimage id (it is the claimant)
+//   HD_DD_REPEAT | j    the preimage of message j (pid[j] is j's id)
+//   HD_DD_FINAL         no preimage: a type outside 1..3
+struct DdPre {
+    uint32_t is_propose;   // 0 or 1
+    int64_t valid_round;   // of a propose, else 0
+    int64_t height, round;
+    uint32_t value[8];
+};
+
+// vround may be NULL: a propose then hashes valid_round -1, as k_fast_prep does
+HD void dd_pre_load(DdPre& k, bool is_propose, const int64_t* height, const int64_t* round, const int64_t* vround,
+                    const uint8_t* value32, size_t i) {
+    k.is_propose = is_propose ? 1u : 0u;
+    k.valid_round = is_propose ? (vround ? vround[i] : -1) : 0;
+    k.height = height[i];
+    k.round = round[i];
+    load_row32_be(k.value, value32, i);
+}
+
+// every byte of the preimage, and which of the two preimage forms it is
+HD bool dd_pre_equal(const DdPre& a, const DdPre& b) {
+    uint32_t d = (a.is_propose ^ b.is_propose) | (uint32_t)(a.valid_round != b.valid_round) |
+                 (uint32_t)(a.height != b.height) | (uint32_t)(a.round != b.round);
+    HD_UNROLL for (int k = 0; k < 8; k++) d |= a.value[k] ^ b.value[k];
+    return d == 0;
+}
+
+// The preimage table's hash: both halves of height and of round, the first
+// and last value word (bytes 0-3, 28-31), the form and the low half of
+// valid_round.  Heights and rounds that differ in their high words only, and
+// the canonical / nil / random values of one round, land on different probe
+// sequences; the compare decides in any case.
+HD uint32_t dd_pre_hash(const DdPre& k) {
+    uint32_t h = ((uint32_t)(uint64_t)k.height) * 0x9E3779B1u;
+    h = (h ^ (uint32_t)((uint64_t)k.height >> 32)) * 0x85EBCA6Bu;
+    h = (h ^ (h >> 15) ^ (uint32_t)(uint64_t)k.round) * 0xC2B2AE35u;
+    h = (h ^ (uint32_t)((uint64_t)k.round >> 32)) * 0x27D4EB2Fu;
+    h = (h ^ (h >> 13) ^ k.value[0]) * 0x165667B1u;
+    h = (h ^ k.value[7]) * 0x9E3779B1u;
+    h = (h ^ (h >> 14) ^ k.is_propose ^ ((uint32_t)(uint64_t)k.valid_round << 1)) * 0x85EBCA6Bu;
+    return h ^ (h >> 16);
+}
+
+// the claimant's id word behind pid word q (q's own when it is an id); the
+// caller loads pid[dd_pid_claimant(q)] when dd_pid_is_ref(q)
+HD bool dd_pid_is_ref(uint32_t q) { return (q >> 30) == 2u; }
+HD bool dd_pid_is_none(uint32_t q) { return (q >> 30) == 3u; }
+HD uint32_t dd_pid_claimant(uint32_t q) { return q & HD_DD_INDEX; }
+HD uint32_t dd_pid_ref(uint32_t claimant) { return HD_DD_REPEAT | claimant; }
+HD uint32_t dd_pid_resolve(const uint32_t* pid, uint32_t i) {
+    uint32_t q = pid[i];
+    if (dd_pid_is_ref(q)) q = pid[dd_pid_claimant(q)];
+    return q;
 }
 
 }  // namespace hd

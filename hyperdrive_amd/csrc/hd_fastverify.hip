@@ -69,13 +69,22 @@ struct FbWork {
     struct Scratch {
         uint32_t* rows = nullptr;     // the split check's per-message rows (SplitRows, 63 words per message)
         size_t cap_rows = 0;
-        uint32_t* dtab = nullptr;     // the repeat table (hd_dedup.h): dd_table_words(n) message indices
+        // the repeat table (hd_dedup.h): dd_table_words(n) message indices,
+        // then the preimage table, as many: one allocation, cleared by one
+        // memset over the tables the call uses
+        uint32_t* dtab = nullptr;
         size_t cap_dtab = 0;
+        // shared preimages: n digest rows (32 bytes, by preimage id), then
+        // pid (n words, by message), then plist (n words, by id: the claimant)
+        uint8_t* pre = nullptr;
+        size_t cap_pre = 0;
         uint32_t* slow = nullptr;     // message index list: the known-key check's leftovers
         size_t cap_slow = 0;
         // device words: [0] leftovers (slow's length), [1] after k_slow_lift,
         // [2] distinct live messages (the compact slots in use), [3] repeats;
-        // [2] and [3] are one 64-bit word to k_fast_prep's atomic
+        // [2] and [3] are one 64-bit word to k_fast_prep's atomic; [4] distinct
+        // preimages (the ids in use), [5] messages without a type 1..3
+        // (k_pre_claim); 8 words
         uint32_t* count = nullptr;
         uint32_t* slow2 = nullptr;    // the leftovers that pass the lift: the full recovery's list
         size_t cap_slow2 = 0;
@@ -109,6 +118,9 @@ struct FbWork {
     // hd_ctx_dedup_stats: [0] messages that entered the known-key check, [1]
     // those served as repeats, since context creation (device, 64-bit)
     unsigned long long* dstats = nullptr;
+    // hd_ctx_preimage_stats: [0] typed messages of the calls that shared
+    // preimages, [1] the distinct preimages they hashed (device, 64-bit)
+    unsigned long long* pstats = nullptr;
     // Ordering between calls (hd_fb_verify): a call waits (on the device) for
     // the last call that used its scratch set.  While keys can still be
     // learned (nr_host != 0), or on the first call after the last key became
@@ -275,14 +287,152 @@ HD uint32_t fb_ref(int d, int w) {
     return d == 0 ? (base | HD_REF_ZERO) : ((base + ad - 1) | (d < 0 ? HD_REF_NEG : 0u));
 }
 
+//
+// Shared preimages (hd_dedup.h).  A call that computes its own
+// digests hashes each distinct preimage once: k_pre_claim gives every typed
+// message a preimage id (pid), k_pre_hash hashes one preimage per lane over
+// the ids in use, and k_fast_prep<true> reads its digest row by id.  Skipping
+// the hash lane by lane in k_fast_prep would save nothing (a wave with one
+// hashing lane issues the whole compression): the hashing lanes are compacted
+// here as the sums' slots are.
+struct PreRows {
+    uint8_t* dig;      // n rows of 32 bytes, by id: the digest, big-endian (a caller's digest row format)
+    uint32_t* pid;     // n, by message (hd_dedup.h)
+    uint32_t* plist;   // n, by id: the claimant's message index
+    uint32_t* cnt;     // Scratch::count: [4] ids in use, [5] messages of this call without a type 1..3
+};
+
+// one message per lane: the preimage table's probe, the ids and pid.  Blocks
+// of HD_PRE_BLOCK lanes: the blocks' atomics all land on the one id counter,
+// so a block is as large as a block can be and adds to the second counter
+// only what is rare (1M messages, alone on the chip: 117 us with two atomics
+// per block of 256, 105 us so).
+#define HD_PRE_BLOCK 1024
+__global__ __launch_bounds__(HD_PRE_BLOCK) void k_pre_claim(DevBatch b, PreRows pre, uint32_t* __restrict__ ptab,
+                                                   uint32_t pmask, int prio) {
+    wave_prio(prio);
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool present = i < b.n;   // (no early exit: the block's lanes meet at the id counter below)
+    const uint32_t type = present ? b.type[i] : 0u;
+    const bool typed = type >= 1 && type <= 3;
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint32_t rep = HD_DD_EMPTY, h = 0;
+    DdPre me;
+    me.is_propose = 0;
+    me.valid_round = me.height = me.round = 0;
+    HD_UNROLL for (int k = 0; k < 8; k++) me.value[k] = 0;
+    if (typed) {
+        dd_pre_load(me, type == T_PROPOSE, b.height, b.round, b.valid_round, b.value32, i);
+        h = dd_pre_hash(me);
+    }
+    // The probe of one lane: true when the message found its preimage or
+    // claimed a slot, false past the cutoff.  The fields compared are the
+    // caller's input arrays, which no kernel writes: no ordering with the
+    // claimant's lane is needed.
+    auto probe = [&]() -> bool {
+        HD_NOUNROLL for (uint32_t p = 0; p < HD_DD_PROBES; p++) {
+            const uint32_t cur = atomicCAS(&ptab[(h + p) & pmask], HD_DD_EMPTY, i);
+            if (cur == HD_DD_EMPTY) return true;   // claimed
+            DdPre other;
+            dd_pre_load(other, b.type[cur] == T_PROPOSE, b.height, b.round, b.valid_round, b.value32, cur);
+            if (dd_pre_equal(me, other)) {
+                rep = cur;
+                return true;
+            }
+        }
+        return false;
+    };
+    // Consecutive messages mostly share a preimage (a round's votes arrive
+    // together), and 64 lanes that compare-and-swap one address serialise at
+    // the memory side.  So only the head of a run probes: a lane whose
+    // preimage differs from the lane's before it (every byte compared), or
+    // the wave's first lane.  The lanes of its run take its claimant, or it
+    // as theirs; when it gave up at the cutoff they count on their own, as
+    // their own probes would have ended.
+    auto up = [&](uint32_t x) { return (uint32_t)__shfl_up((int)x, 1); };
+    auto up64 = [&](int64_t x) {
+        return (int64_t)((uint64_t)up((uint32_t)((uint64_t)x >> 32)) << 32 | up((uint32_t)(uint64_t)x));
+    };
+    DdPre pk;
+    pk.is_propose = up(me.is_propose);
+    pk.valid_round = up64(me.valid_round);
+    pk.height = up64(me.height);
+    pk.round = up64(me.round);
+    HD_UNROLL for (int k = 0; k < 8; k++) pk.value[k] = up(me.value[k]);
+    const bool prev_typed = up(typed ? 1u : 0u) != 0u;
+    const bool head = typed && (lane == 0 || !prev_typed || !dd_pre_equal(me, pk));
+    uint32_t found = 0;
+    if (head) found = probe() ? 1u : 0u;
+    // a typed lane that is no head follows a typed lane with an equal key:
+    // the run reaches back to a head (the first lane, when typed, is one)
+    const unsigned long long hm = __ballot(head) & ((2ull << lane) - 1ull);
+    const int hl = hm ? 63 - __clzll((long long)hm) : 0;
+    const uint32_t hrep = (uint32_t)__shfl((int)rep, hl), hfound = (uint32_t)__shfl((int)found, hl);
+    if (typed && !head && hfound) rep = hrep == HD_DD_EMPTY ? i - lane + (uint32_t)hl : hrep;
+    // ids: one atomic per block adds its claimants (returned: the block's
+    // first id), another its messages without a type 1..3, if any (the typed
+    // ones are the rest of n); a lane's id follows from the ballots
+    const bool claimant = typed && rep == HD_DD_EMPTY;
+    __shared__ uint32_t s_cnt[HD_PRE_BLOCK / 64], s_base;
+    const unsigned long long bc = __ballot(claimant), bu = __ballot(present && !typed);
+    if (lane == 0) s_cnt[wv] = (uint32_t)__popcll(bc) | (uint32_t)__popcll(bu) << 16;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (uint32_t w = 0; w < HD_PRE_BLOCK / 64; w++) t += s_cnt[w];   // (<= 1024 each half: no carry)
+        s_base = 0;
+        if (t & 0xFFFFu) s_base = atomicAdd(pre.cnt + 4, t & 0xFFFFu);
+        if (t >> 16) atomicAdd(pre.cnt + 5, t >> 16);
+    }
+    __syncthreads();
+    if (!present) return;
+    if (claimant) {
+        uint32_t id = s_base + (uint32_t)__popcll(bc & ((1ull << lane) - 1ull));
+        for (uint32_t w = 0; w < wv; w++) id += s_cnt[w] & 0xFFFFu;
+        pre.plist[id] = i;
+        pre.pid[i] = id;
+    } else {
+        pre.pid[i] = typed ? dd_pid_ref(rep) : HD_DD_FINAL;
+    }
+}
+
+// one distinct preimage per lane: the grid is sized for n and the waves past
+// the ids in use exit here.  (stats: the first lane adds the call to the
+// context's cumulative counters.)
+__global__ __launch_bounds__(256) void k_pre_hash(DevBatch b, PreRows pre, unsigned long long* __restrict__ stats,
+                                                  int prio) {
+    wave_prio(prio);
+    const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nd = pre.cnt[4];
+    if (id == 0) {
+        const uint32_t typed = b.n - pre.cnt[5];
+        if (typed) atomicAdd(&stats[0], (unsigned long long)typed);
+        if (nd) atomicAdd(&stats[1], (unsigned long long)nd);
+    }
+    if (id >= nd) return;
+    const uint32_t i = pre.plist[id];
+    uint32_t value[8], out[8];
+    load_row32_be(value, b.value32, i);
+    if (b.type[i] == T_PROPOSE)
+        sha256_propose(out, b.height[i], b.round[i], b.valid_round ? b.valid_round[i] : -1, value);
+    else
+        sha256_vote(out, b.height[i], b.round[i], value);
+    store_row32_be(pre.dig, id, out);
+}
+
 // one message per lane (occupancy hides the lookup's dependent loads): type,
-// admitted lookup, key state, digest, the early checks; m and r to the rows
+// admitted lookup, key state, digest, the early checks; m and r to the rows.
+// SHARE: the digest is the row of the message's preimage id (PreRows; no SHA
+// code in the kernel), and the id stands for (height, round, value) in the
+// repeat compare: equal ids are equal preimages, and equal preimages that
+// missed each other at the preimage table's cutoff are merely not merged.
+template <bool SHARE>
 __global__ __launch_bounds__(256) void k_fast_prep(DevBatch b, const uint8_t* __restrict__ digest_in,
                                                    const uint32_t* __restrict__ state,
                                                    const int32_t* __restrict__ adm_slot, AdmIndex ix,
                                                    uint32_t n_adm, SplitRows rows, const uint32_t* __restrict__ fdict,
                                                    uint32_t* __restrict__ fhit, uint32_t fbase,
-                                                   uint32_t* __restrict__ dtab, uint32_t dmask) {
+                                                   uint32_t* __restrict__ dtab, uint32_t dmask, PreRows pre) {
     wave_prio(rows.prio);
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t n = b.n;
@@ -310,9 +460,15 @@ __global__ __launch_bounds__(256) void k_fast_prep(DevBatch b, const uint8_t* __
             slot = (uint32_t)sl;
             if (idx == -2) atomicAdd(&fhit[sl - (int32_t)fbase], 1u);   // a foreign slot's use (fb_evict)
             FastIn in;
-            DdKey me;   // this message's inputs, as the repeat table compares them
+            // this message's inputs, as the repeat table compares them: the
+            // preimage id stands for (height, round, value) when shared
+            DdKey me;
+            uint32_t my_id = 0;
             me.height = me.round = 0;
-            if (digest_in) {
+            if constexpr (SHARE) {
+                my_id = dd_pid_resolve(pre.pid, i);
+                load_row32_be(in.digest_be, pre.dig, my_id);
+            } else if (digest_in) {
                 load_row32_be(in.digest_be, digest_in, i);
                 HD_UNROLL for (int k = 0; k < 8; k++) me.value[k] = in.digest_be[k];
             } else {
@@ -337,19 +493,36 @@ __global__ __launch_bounds__(256) void k_fast_prep(DevBatch b, const uint8_t* __
                 // with the claimant's lane.  Proposes are never merged (their
                 // preimage has valid_round).  dtab is NULL with HD_VAR_DEDUP 0.
                 if (dtab && type != T_PROPOSE) {
-                    HD_UNROLL for (int k = 0; k < 8; k++) {
-                        me.from[k] = from_be[k];
-                        me.r[k] = in.r_be[k];
-                        me.s[k] = in.s_be[k];
+                    if constexpr (!SHARE) {
+                        HD_UNROLL for (int k = 0; k < 8; k++) {
+                            me.from[k] = from_be[k];
+                            me.r[k] = in.r_be[k];
+                            me.s[k] = in.s_be[k];
+                        }
+                        me.v = in.v;
                     }
-                    me.v = in.v;
-                    const uint32_t h = dd_hash(me);
+                    const uint32_t h = dd_hash_words(in.r_be[0], in.r_be[7], in.s_be[0], in.s_be[7], from_be[0], from_be[7]);
                     HD_NOUNROLL for (uint32_t p = 0; p < HD_DD_PROBES; p++) {
                         const uint32_t cur = atomicCAS(&dtab[(h + p) & dmask], HD_DD_EMPTY, i);
                         if (cur == HD_DD_EMPTY) break;   // claimed: distinct
-                        DdKey other;
-                        dd_key_load(other, b.height, b.round, b.value32, digest_in, b.from32, b.sig65, cur, n);
-                        if (dd_key_equal(me, other)) {
+                        bool eq;
+                        if constexpr (SHARE) {
+                            // dd_key_equal's compare with the ids in place of
+                            // (height, round, value), field by field against
+                            // this lane's live registers: the differences are
+                            // ORed as the claimant's words arrive
+                            uint32_t d = dd_pid_resolve(pre.pid, cur) ^ my_id, w[8], w2[8], v2;
+                            load_row32_be(w, b.from32, cur);
+                            HD_UNROLL for (int k = 0; k < 8; k++) d |= w[k] ^ from_be[k];
+                            load_sig65(w, w2, v2, b.sig65, cur, n);
+                            HD_UNROLL for (int k = 0; k < 8; k++) d |= (w[k] ^ in.r_be[k]) | (w2[k] ^ in.s_be[k]);
+                            eq = (d | (v2 ^ in.v)) == 0;
+                        } else {
+                            DdKey other;
+                            dd_key_load(other, b.height, b.round, b.value32, digest_in, b.from32, b.sig65, cur, n);
+                            eq = dd_key_equal(me, other);
+                        }
+                        if (eq) {
                             rep = cur;
                             break;
                         }
@@ -1337,6 +1510,8 @@ int hd_fb_init(hd_ctx* ctx) {
     FBCHK(hipHostGetDevicePointer((void**)&f->fpend_dev, f->fpend_host, 0), "fb foreign claims map");
     FBCHK(hipMalloc(&f->dstats, 16), "fb repeat counters");
     FBCHK(hipMemset(f->dstats, 0, 16), "fb repeat counters clear");   // (blocking: calls on any stream add to it)
+    FBCHK(hipMalloc(&f->pstats, 16), "fb preimage counters");
+    FBCHK(hipMemset(f->pstats, 0, 16), "fb preimage counters clear");
     int rc = fb_alloc_slots(ctx);
     if (rc) return rc;
     return fb_g_table(ctx, &f->gtab);
@@ -1353,11 +1528,11 @@ void hd_fb_release(hd_ctx* ctx) {
     for (hipEvent_t e : f->ev_sums) (void)hipEventDestroy(e);
     for (auto& sc : f->sc) {
         if (sc.done) (void)hipEventDestroy(sc.done);
-        void* sp[] = {sc.rows, sc.slow, sc.count, sc.slow2, sc.dtab};
+        void* sp[] = {sc.rows, sc.slow, sc.count, sc.slow2, sc.dtab, sc.pre};
         for (void* p : sp)
             if (p) (void)hipFree(p);
     }
-    void* ptrs[] = {f->counts, f->adm_slot, f->zr, f->fdict, f->fnext, f->fhit, f->fkey, f->dstats};
+    void* ptrs[] = {f->counts, f->adm_slot, f->zr, f->fdict, f->fnext, f->fhit, f->fkey, f->dstats, f->pstats};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     if (f->nr_host) (void)hipHostFree(f->nr_host);
@@ -1641,7 +1816,7 @@ static void launch_sums(const hd_ctx* ctx, uint32_t blocks, hipStream_t s, uint3
 template <int K, int WP>
 static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_t* d_verdict,
                          uint8_t* d_rec32, int32_t* d_signer, uint32_t* d_bitmap, const SplitRows& rows,
-                         const FbWork::Scratch& sc, hipStream_t s, bool auth) {
+                         const FbWork::Scratch& sc, hipStream_t s, bool auth, bool share) {
     FbWork* f = ctx->fb;
     const uint32_t n = b.n;
     // The middle kernels run over the slots in use, which only the device
@@ -1649,9 +1824,21 @@ static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest
     const uint32_t tb = (split_lanes<K>(n) + 255) / 256, nb = (n + 255) / 256;
     // HD_VAR_DEDUP 0: no table, so no message is ever marked a repeat; slots,
     // ref and every kernel are the same
+    const uint32_t tw = dd_table_words(n);
     uint32_t* dtab = ctx->var[HD_VAR_DEDUP] ? sc.dtab : nullptr;
-    k_fast_prep<<<nb, 256, 0, s>>>(b, d_digest, f->state, f->adm_slot, hd_adm_index(ctx), ctx->n_adm, rows,
-                                   f->fcap ? f->fdict : nullptr, f->fhit, f->fbase, dtab, dd_table_words(n) - 1u);
+    const uint32_t* fdict = f->fcap ? f->fdict : nullptr;
+    if (share) {
+        // HD_VAR_PRE_SHARE 1 and no caller digests: each distinct preimage is
+        // hashed once (k_pre_claim, k_pre_hash), k_fast_prep reads the rows
+        const PreRows pre{sc.pre, (uint32_t*)(sc.pre + 32 * (size_t)n), (uint32_t*)(sc.pre + 36 * (size_t)n), sc.count};
+        k_pre_claim<<<(n + HD_PRE_BLOCK - 1) / HD_PRE_BLOCK, HD_PRE_BLOCK, 0, s>>>(b, pre, sc.dtab + tw, tw - 1u, rows.prio);
+        k_pre_hash<<<nb, 256, 0, s>>>(b, pre, f->pstats, rows.prio);
+        k_fast_prep<true><<<nb, 256, 0, s>>>(b, nullptr, f->state, f->adm_slot, hd_adm_index(ctx), ctx->n_adm, rows,
+                                             fdict, f->fhit, f->fbase, dtab, tw - 1u, pre);
+    } else {
+        k_fast_prep<false><<<nb, 256, 0, s>>>(b, d_digest, f->state, f->adm_slot, hd_adm_index(ctx), ctx->n_adm, rows,
+                                              fdict, f->fhit, f->fbase, dtab, tw - 1u, PreRows{});
+    }
     k_fast_sinv<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
     hipEvent_t* pe = fb_prof_pair(f->ev_sums, f->n_sums, f->prof);
     if (pe) (void)hipEventRecord(pe[0], s);
@@ -1675,7 +1862,7 @@ int hd_fb_verify(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_
     f->next = (j + 1) % FbWork::NSCRATCH;
     FbWork::Scratch& sc = f->sc[j];
     if (!sc.done) FBCHK(hipEventCreateWithFlags(&sc.done, hipEventDisableTiming), "fb scratch event");
-    if (!sc.count) FBCHK(hipMalloc(&sc.count, 16), "fb scratch count");
+    if (!sc.count) FBCHK(hipMalloc(&sc.count, 32), "fb scratch count");
     // foreign slots re-keyed (fb_evict; it waited for every earlier call)
     bool evicted = false;
     int re = fb_evict(ctx, &evicted);
@@ -1720,7 +1907,7 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
     const uint32_t blocks = (b.n + 255) / 256;
     rc = hd_dev_grow(ctx, (void**)&sc.slow2, &sc.cap_slow2, 4 * (size_t)b.n);
     if (rc) return rc;
-    FBCHK(hipMemsetAsync(sc.count, 0, 16, s), "fb count reset");
+    FBCHK(hipMemsetAsync(sc.count, 0, 32, s), "fb count reset");
     if (ctx->n_adm > 0 && f->adm_slot && f->map_ok) {
         if (b.n > HD_DD_MAX_N) {   // ref's encoding (hd_dedup.h); the rows of such a batch exceed the device anyway
             ctx->last_error = "known-key check: more than 2^30 messages in one call";
@@ -1730,11 +1917,19 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
         rc = hd_dev_grow(ctx, (void**)&sc.rows, &sc.cap_rows, 4 * row_words * (size_t)b.n);
         if (rc) return rc;
         const uint32_t n = b.n;
-        if (ctx->var[HD_VAR_DEDUP]) {
+        // the repeat table, then the preimage table: one allocation, and one
+        // clear over the tables this call uses
+        const bool share = ctx->var[HD_VAR_PRE_SHARE] && !d_digest;
+        if (ctx->var[HD_VAR_DEDUP] || share) {
             const size_t tab_bytes = 4 * (size_t)dd_table_words(n);
-            rc = hd_dev_grow(ctx, (void**)&sc.dtab, &sc.cap_dtab, tab_bytes);
+            rc = hd_dev_grow(ctx, (void**)&sc.dtab, &sc.cap_dtab, 2 * tab_bytes);
             if (rc) return rc;
-            FBCHK(hipMemsetAsync(sc.dtab, 0xFF, tab_bytes, s), "fb repeat table clear");
+            const size_t first = ctx->var[HD_VAR_DEDUP] ? 0 : tab_bytes, last = share ? 2 * tab_bytes : tab_bytes;
+            FBCHK(hipMemsetAsync((uint8_t*)sc.dtab + first, 0xFF, last - first, s), "fb table clear");
+        }
+        if (share) {
+            rc = hd_dev_grow(ctx, (void**)&sc.pre, &sc.cap_pre, 40 * (size_t)n);
+            if (rc) return rc;
         }
         SplitRows rows;
         rows.aux = sc.rows;
@@ -1749,7 +1944,7 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
         rows.prio = ctx->var[HD_VAR_WAVE_PRIO];
         const int k = split_k_for(ctx, n);
         f->last_k = k;
-#define HD_SPLIT(K, WP) launch_split<K, WP>(ctx, b, d_digest, d_verdict, d_rec32, d_signer, d_bitmap, rows, sc, s, auth)
+#define HD_SPLIT(K, WP) launch_split<K, WP>(ctx, b, d_digest, d_verdict, d_rec32, d_signer, d_bitmap, rows, sc, s, auth, share)
         if (f->wp == HD_FB_WX) {
             if (k == 16) HD_SPLIT(16, HD_FB_WX);
             else HD_SPLIT(8, HD_FB_WX);
@@ -1916,6 +2111,21 @@ int hd_ctx_dedup_stats(hd_ctx* ctx, uint64_t* checked, uint64_t* repeats) {
     FBCHK(hipMemcpy(st, ctx->fb->dstats, 16, hipMemcpyDeviceToHost), "repeat counters read");
     if (checked) *checked = st[0];
     if (repeats) *repeats = st[1];
+    return HD_OK;
+}
+
+int hd_ctx_preimage_stats(hd_ctx* ctx, uint64_t* typed, uint64_t* distinct) {
+    if (!ctx) return HD_EINVAL;
+    if (typed) *typed = 0;
+    if (distinct) *distinct = 0;
+    if (!ctx->fb || !ctx->fb->pstats) return HD_OK;
+    (void)hipSetDevice(ctx->device);
+    int rq = hd_ctx_quiesce(ctx);
+    if (rq) return rq;
+    unsigned long long st[2] = {0, 0};
+    FBCHK(hipMemcpy(st, ctx->fb->pstats, 16, hipMemcpyDeviceToHost), "preimage counters read");
+    if (typed) *typed = st[0];
+    if (distinct) *distinct = st[1];
     return HD_OK;
 }
 

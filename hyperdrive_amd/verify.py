@@ -430,7 +430,8 @@ class Verifier:
 
     # include/hd_verify.h HD_VAR_*: kernel variants of this context
     VARIANTS = {"verify_waves": 0, "sum_waves": 1, "sum_prefetch": 2, "split_k": 4, "recover_g": 5,
-                "key_width": 7, "wave_prio": 8, "foreign_keys": 10, "slow_lift": 11, "dedup": 12}
+                "key_width": 7, "wave_prio": 8, "foreign_keys": 10, "slow_lift": 11, "dedup": 12,
+                "pre_share": 15}
 
     def set_variant(self, name: str, value: int) -> None:
         """Select a compiled kernel variant (A/B, variant tests); see
@@ -483,6 +484,15 @@ class Verifier:
         c, r = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self._lib.hd_ctx_dedup_stats(self._ctx, ctypes.byref(c), ctypes.byref(r)), "hd_ctx_dedup_stats")
         return int(c.value), int(r.value)
+
+    def preimage_stats(self) -> Tuple[int, int]:
+        """(typed messages of the calls that shared preimages, the distinct
+        preimages those calls hashed), cumulative since the context was
+        created (include/hd_verify.h hd_ctx_preimage_stats)."""
+        t, d = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.hd_ctx_preimage_stats(self._ctx, ctypes.byref(t), ctypes.byref(d)),
+                    "hd_ctx_preimage_stats")
+        return int(t.value), int(d.value)
 
     def fastpath_geometry(self) -> Tuple[int, int, int]:
         """(G table windows, per-key table windows, messages sharing one

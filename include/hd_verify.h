@@ -156,6 +156,12 @@ int hd_ctx_foreign_stats(hd_ctx* ctx, uint32_t* ready_slots, uint32_t* evictions
  * its check.  checked - repeats is the number of checks executed.  Either may
  * be NULL; synchronises the context's calls. */
 int hd_ctx_dedup_stats(hd_ctx* ctx, uint64_t* checked, uint64_t* repeats);
+/* Shared preimages of the known-key check (HD_VAR_PRE_SHARE), cumulative since
+ * context creation, from device counters: typed = messages with a type in
+ * 1..3 of the calls that shared preimages (those without caller digests),
+ * distinct = the preimages those calls hashed (one SHA-256 each, two blocks
+ * for a propose).  Either may be NULL; synchronises the context's calls. */
+int hd_ctx_preimage_stats(hd_ctx* ctx, uint64_t* typed, uint64_t* distinct);
 /* Shape of the known-key check as the context runs it now (for cost models):
  * g_windows / key_windows: fixed-base windows of the G table and of the
  * per-key tables (one table point each; the first is loaded, the rest are
@@ -213,11 +219,16 @@ int hd_ctx_profile(hd_ctx* ctx, int enable);
                                    replay) is checked once and every copy gets that check's outputs; 0 no
                                    message is ever marked a repeat (same kernels, same compaction)
                                    [HD_DEDUP] */
+#define HD_VAR_PRE_SHARE 15     /* digests of the known-key check: 1 (default) a call without caller digests
+                                   hashes each distinct preimage (height, round, value; valid_round too for a
+                                   propose) once and every message reads its digest by preimage id; 0 every
+                                   message hashes its own (the operator's switch: no adaptive rule)
+                                   [HD_PRE_SHARE] */
 /* Keys 3, 6, 9, 13 and 14 (the digit pass, the paired kernel's waves, the
  * sums residency cap, the lean inversions and the sums chain) were measured
  * without gain and removed in round 5: set returns HD_EINVAL for them, get
  * returns their fixed value. */
-#define HD_VAR__COUNT 15
+#define HD_VAR__COUNT 16
 int hd_ctx_set_variant(hd_ctx* ctx, int which, int value);
 int hd_ctx_get_variant(hd_ctx* ctx, int which, int* value);
 int hd_ctx_profile_read(hd_ctx* ctx, uint32_t* calls, double* verify_ms, uint32_t* sums_launches, double* sums_ms);
