@@ -132,6 +132,20 @@ struct FbWork {
     hipStream_t last = nullptr;
     bool any = false;
     bool steady = false;          // the previous call ran with nothing to learn
+    // HD_VAR_SUM_CHAIN: a call's k_fast_sums waits for the previous call's
+    // when that call launched one on another stream, so one call's sums runs
+    // at a time and the other calls' short kernels run beside it instead of
+    // in lockstep with each other.  sums_done is recorded right after a
+    // chained launch; sums_prev says that the previous call recorded it (a
+    // call without a launch -- no admitted set, an early error return --
+    // leaves it false, and the next call does not wait).  A wait only ever
+    // names work submitted earlier, so the order between calls stays acyclic.
+    // The event is older than the call events (done, Scratch::done) of its
+    // call, so whoever waits for those has waited for it.
+    hipEvent_t sums_done = nullptr;
+    hipStream_t sums_last = nullptr;
+    bool sums_prev = false, sums_now = false;
+    uint32_t n_capped = 0, n_lean = 0, n_chained = 0;   // hd_ctx_overlap_stats
     // hd_ctx_profile: event pairs around whole calls and around k_fast_sums
     bool prof = false;
     std::vector<hipEvent_t> ev_call, ev_sums;
@@ -855,6 +869,122 @@ __global__ __launch_bounds__(256) void k_fast_zinv(uint32_t n, SplitRows rows) {
     });
 }
 
+// Lean forms of the two inversion kernels (HD_VAR_LEAN_INV): the same
+// inverses from one inversion per lane over the same lanes and slots, but a
+// linear walk whose prefix products go through the pre row of each message
+// (which receives that message's inverse on the way back) instead of K
+// inputs and K prefixes, or a product tree, in registers.  The launch bound
+// holds them to 168 VGPRs where k_fast_sinv / k_fast_zinv take 368 / 397, so
+// a wave of either fits beside two waves per SIMD of a running k_fast_sums
+// (HD_VAR_SUM_CAP) and one call's inversions run beside another call's sums.
+// A lane reads back only what it stored itself.
+HD bool lean_live(const SplitRows& rows, uint32_t nc, uint32_t i) {
+    return i < nc && (rows.aux[i] & 0xFFu) == HD_FAST_LIVE;
+}
+
+template <int K>
+__global__ __launch_bounds__(256, 3) void k_fast_sinv_lean(uint32_t n, SplitRows rows, uint32_t* __restrict__ est,
+                                                           unsigned long long* __restrict__ stats) {
+    wave_prio(rows.prio);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
+    if (t == 0) {   // as k_fast_sinv
+        const uint32_t reps = rows.cnt[3];
+        if (est) {
+            est[1] = n;
+            est[0] = nc;
+        }
+        if (nc + reps) atomicAdd(&stats[0], (unsigned long long)nc + reps);
+        if (reps) atomicAdd(&stats[1], (unsigned long long)reps);
+    }
+    if (t >= T) return;
+    uint32_t live = 0;
+    sm acc;
+    HD_UNROLL for (int k = 0; k < 9; k++) acc.n[k] = 0;
+    HD_NOUNROLL for (int j = 0; j < K; j++) {
+        const uint32_t i = (uint32_t)j * T + t;
+        if (!lean_live(rows, nc, i)) continue;
+        sc s;
+        soa_load(s.v, rows.s, n, i);
+        sm ss;
+        sm_from_sc(ss, s);
+        if (live) sm_mul(acc, acc, ss);
+        else acc = ss;
+        live |= 1u << j;
+        soa_store(rows.pre, n, i, acc.n);   // the product of the live messages up to j
+    }
+    if (!live) return;
+    sm inv;
+    {
+        sc p, pinv;
+        sm_to_sc(p, acc);
+        sc_inv_divsteps(pinv, p);   // a product of scalars in [1, n) times R^-k: never 0
+        sm_from_sc(inv, pinv);
+        sm r2;
+        sm_r2(r2);
+        sm_mul(inv, inv, r2);
+    }
+    HD_NOUNROLL for (int j = K - 1; j >= 0; j--) {
+        if (!((live >> j) & 1u)) continue;
+        const uint32_t i = (uint32_t)j * T + t;
+        const uint32_t below = live & ((1u << j) - 1u);
+        if (below) {   // a live message before this one: the highest such holds the prefix
+            const uint32_t ip = (uint32_t)(31 - __clz((int)below)) * T + t;
+            sm pp, sinv, ss;
+            soa_load(pp.n, rows.pre, n, ip);
+            sc s;
+            soa_load(s.v, rows.s, n, i);
+            sm_mul(sinv, inv, pp);
+            sm_from_sc(ss, s);
+            sm_mul(inv, inv, ss);
+            soa_store(rows.pre, n, i, sinv.n);
+        } else {
+            soa_store(rows.pre, n, i, inv.n);
+        }
+    }
+}
+
+template <int K>
+__global__ __launch_bounds__(256, 3) void k_fast_zinv_lean(uint32_t n, SplitRows rows) {
+    wave_prio(rows.prio);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
+    if (t >= T) return;
+    const uint32_t* zrow = rows.xyz + 18 * (size_t)n;
+    uint32_t live = 0;
+    fe acc;
+    HD_UNROLL for (int k = 0; k < 9; k++) acc.n[k] = 0;
+    HD_NOUNROLL for (int j = 0; j < K; j++) {
+        const uint32_t i = (uint32_t)j * T + t;
+        if (!lean_live(rows, nc, i)) continue;
+        fe z;
+        soa_load(z.n, zrow, n, i);
+        if (live) fe_mul(acc, acc, z);
+        else acc = z;
+        live |= 1u << j;
+        soa_store(rows.pre, n, i, acc.n);
+    }
+    if (!live) return;
+    fe inv;
+    fe_inv_divsteps(inv, acc);   // a product of non-zero Z: never 0
+    HD_NOUNROLL for (int j = K - 1; j >= 0; j--) {
+        if (!((live >> j) & 1u)) continue;
+        const uint32_t i = (uint32_t)j * T + t;
+        const uint32_t below = live & ((1u << j) - 1u);
+        if (below) {
+            const uint32_t ip = (uint32_t)(31 - __clz((int)below)) * T + t;
+            fe pp, zi, z;
+            soa_load(pp.n, rows.pre, n, ip);
+            soa_load(z.n, zrow, n, i);
+            fe_mul(zi, inv, pp);
+            fe_mul(inv, inv, z);
+            soa_store(rows.pre, n, i, zi.n);
+        } else {
+            soa_store(rows.pre, n, i, inv.n);
+        }
+    }
+}
+
 // x = r (+ n when v & 2) as a field element: the x coordinate of R (the range
 // checks of sig_prefix passed in k_fast_prep)
 HD void fast_rx(fe& x, const sc& r, uint32_t v) {
@@ -1524,6 +1654,7 @@ void hd_fb_release(hd_ctx* ctx) {
     FbWork* f = ctx->fb;
     fb_free_tables(ctx);
     if (f->done) (void)hipEventDestroy(f->done);
+    if (f->sums_done) (void)hipEventDestroy(f->sums_done);
     for (hipEvent_t e : f->ev_call) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_sums) (void)hipEventDestroy(e);
     for (auto& sc : f->sc) {
@@ -1793,30 +1924,79 @@ static uint32_t fallback_blocks(uint32_t est, uint32_t full) {
     return (uint32_t)std::min<uint64_t>(full, std::max<uint64_t>(want, std::min(64u, full)));
 }
 
-// k_fast_sums occupancy (HD_VAR_SUM_WAVES) and prefetch depth (HD_VAR_SUM_PREFETCH)
+// k_fast_sums waves per SIMD for a batch of n (HD_VAR_SUM_WAVES).
+// 0 (the default): 4 waves per SIMD for a batch that fills fewer than two
+// rounds at 3 (C3's 128k messages: +5 %; measured 3 % slower per 1M, where
+// 3 waves keep the loaded-ahead table points)
+static int sums_waves(const hd_ctx* ctx, uint32_t n) {
+    const int w = ctx->var[HD_VAR_SUM_WAVES];
+    if (w) return w;
+    return (uint64_t)n < 2ull * 3 * 4 * 64 * (uint64_t)std::max(ctx->n_cu, 1) ? 4 : 3;
+}
+
+// Whether a call of n messages takes the overlap path (HD_VAR_SUM_CAP,
+// HD_VAR_LEAN_INV, HD_VAR_SUM_CHAIN, each where its variant is on): not with
+// the 4-wave sums (small batches), and not while the latest call left more
+// than 1 / 128 of its size over from the known-key check (FbWork::est_host[0]; none
+// seen yet counts as none).  Those recoveries' waves sit on the SIMDs for
+// more than a sums' length, and with one capped sums at a time the chip runs
+// short of work beside them: C5 (30 % adversarial) measured 10 % slower on
+// the overlap path, so such traffic keeps the path without it (DESIGN 5,
+// round 12).  Authentication calls (the ingress, whose pushes alternate with
+// the message queue's many short kernels) keep that path too: the ingress
+// line measured 1-8 % slower on the overlap path in three pairs of runs.
+// Evaluated once per call, when it is submitted (fb_verify_impl), and handed
+// down.  The estimate is pinned memory the device writes as earlier calls
+// run, so which path a call takes -- its speed, never its outputs -- depends
+// on how far those calls have come and is not reproducible from run to run
+// while calls with many leftovers are in flight.
+static bool sums_overlap(const hd_ctx* ctx, uint32_t n) {
+    if (sums_waves(ctx, n) == 4) return false;
+    const uint32_t est = ctx->fb->est_host ? *(volatile uint32_t*)ctx->fb->est_host : 0xFFFFFFFFu;
+    return est == 0xFFFFFFFFu || (uint64_t)est * 128 <= n;
+}
+
+// HD_VAR_SUM_CAP: the dynamic LDS that holds the 3-wave k_fast_sums at two
+// 256-lane blocks per CU (two waves per SIMD, 2 x 168 of its 512 VGPRs; 176
+// stay free for other kernels' waves).  A block reserves HD_SUMS_CAP_LDS in
+// all, `stat` bytes of it the kernel's own digit array: two such blocks fit
+// the CU's 160 KiB (MI355X: HD_CU_LDS) and a third does not, whatever the
+// allocation granule up to 4 KiB, and 40 KiB stay for the other kernels'
+// blocks (under 1 KiB each).  The kernel never addresses the reservation.
+#define HD_CU_LDS (160u * 1024u)
+#define HD_SUMS_CAP_LDS (60u * 1024u)
+static_assert(2 * HD_SUMS_CAP_LDS <= HD_CU_LDS && 3 * HD_SUMS_CAP_LDS > HD_CU_LDS + 2 * 4096, "two blocks per CU");
+static_assert(HD_SUMS_CAP_LDS <= 64u * 1024u, "the LDS limit of one block");
+template <int WP>
+static constexpr size_t sums_cap_lds() {
+    constexpr size_t stat = 4 * 256 * (size_t)(FbL<HD_FB_WG>::NWIN + FbL<WP>::NWIN);   // k_fast_sums' sdig
+    static_assert(stat < HD_SUMS_CAP_LDS, "k_fast_sums' digit array exceeds the capped block's LDS");
+    return HD_SUMS_CAP_LDS - stat;
+}
+
+// k_fast_sums occupancy (sums_waves), prefetch depth (HD_VAR_SUM_PREFETCH)
+// and residency cap (HD_VAR_SUM_CAP: the 3-wave forms only)
 template <int WP>
 static void launch_sums(const hd_ctx* ctx, uint32_t blocks, hipStream_t s, uint32_t n, const gp* gtab,
-                        const gp* const* tab, const SplitRows& rows) {
-    // 0 (the default): 4 waves per SIMD for a batch that fills fewer than two
-    // rounds at 3 (C3's 128k messages: +5 %; measured 3 % slower per 1M, where
-    // 3 waves keep the loaded-ahead table points)
-    int w = ctx->var[HD_VAR_SUM_WAVES];
+                        const gp* const* tab, const SplitRows& rows, bool overlap) {
+    const int w = sums_waves(ctx, n);
     const int pf = ctx->var[HD_VAR_SUM_PREFETCH];
-    if (w == 0) w = (uint64_t)n < 2ull * 3 * 4 * 64 * (uint64_t)std::max(ctx->n_cu, 1) ? 4 : 3;
+    const size_t cap = ctx->var[HD_VAR_SUM_CAP] && overlap && w == 3 ? sums_cap_lds<WP>() : 0;
+    if (cap) ctx->fb->n_capped++;
     if (pf == 2) {
         if (w == 2) k_fast_sums<2, WP, 2><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
-        else k_fast_sums<3, WP, 2><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);   // (no 4-wave form)
+        else k_fast_sums<3, WP, 2><<<blocks, 256, cap, s>>>(n, gtab, tab, rows);   // (no 4-wave form)
     } else {
         if (w == 2) k_fast_sums<2, WP, 1><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
         else if (w == 4) k_fast_sums<4, WP, 0><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
-        else k_fast_sums<3, WP, 1><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
+        else k_fast_sums<3, WP, 1><<<blocks, 256, cap, s>>>(n, gtab, tab, rows);
     }
 }
 
 template <int K, int WP>
 static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_t* d_verdict,
                          uint8_t* d_rec32, int32_t* d_signer, uint32_t* d_bitmap, const SplitRows& rows,
-                         const FbWork::Scratch& sc, hipStream_t s, bool auth, bool share) {
+                         const FbWork::Scratch& sc, hipStream_t s, bool auth, bool share, bool overlap) {
     FbWork* f = ctx->fb;
     const uint32_t n = b.n;
     // The middle kernels run over the slots in use, which only the device
@@ -1839,12 +2019,30 @@ static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest
         k_fast_prep<false><<<nb, 256, 0, s>>>(b, d_digest, f->state, f->adm_slot, hd_adm_index(ctx), ctx->n_adm, rows,
                                               fdict, f->fhit, f->fbase, dtab, tw - 1u, PreRows{});
     }
-    k_fast_sinv<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
+    // HD_VAR_LEAN_INV: the inversion kernels that fit beside a capped sums;
+    // a call that takes the 4-wave sums (a small batch) keeps the register
+    // forms and stays out of the chain below
+    const bool lean = ctx->var[HD_VAR_LEAN_INV] && overlap;
+    if (lean) f->n_lean++;
+    if (lean) k_fast_sinv_lean<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
+    else k_fast_sinv<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
+    // HD_VAR_SUM_CHAIN (see FbWork): behind the previous call's sums when it
+    // ran on another stream; before the profile pair, so the pair times the
+    // kernel and not the wait.  Without the event (creation failed) the call
+    // runs unchained.
+    const bool chain = ctx->var[HD_VAR_SUM_CHAIN] && overlap &&
+                       (f->sums_done || hipEventCreateWithFlags(&f->sums_done, hipEventDisableTiming) == hipSuccess);
+    if (chain && f->sums_prev && f->sums_last != s && hipStreamWaitEvent(s, f->sums_done, 0) == hipSuccess) f->n_chained++;
     hipEvent_t* pe = fb_prof_pair(f->ev_sums, f->n_sums, f->prof);
     if (pe) (void)hipEventRecord(pe[0], s);
-    launch_sums<WP>(ctx, nb, s, n, f->gtab, f->tabs, rows);
+    launch_sums<WP>(ctx, nb, s, n, f->gtab, f->tabs, rows, overlap);
     if (pe) (void)hipEventRecord(pe[1], s);
-    k_fast_zinv<K><<<tb, 256, 0, s>>>(n, rows);
+    if (chain && hipEventRecord(f->sums_done, s) == hipSuccess) {
+        f->sums_last = s;
+        f->sums_now = true;
+    }
+    if (lean) k_fast_zinv_lean<K><<<tb, 256, 0, s>>>(n, rows);
+    else k_fast_zinv<K><<<tb, 256, 0, s>>>(n, rows);
     // whole blocks of 256: every wavefront's 64 messages are one bitmap word pair
     k_fast_cmp<<<nb, 256, 0, s>>>(b, rows, ctx->d_adm_perm, d_verdict, d_rec32, d_signer, sc.slow, sc.count,
                                   d_bitmap, auth);
@@ -1857,6 +2055,10 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
 int hd_fb_verify(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_t* d_verdict, uint8_t* d_rec32,
                  int32_t* d_signer, uint32_t* d_bitmap, hipStream_t s, bool auth) {
     FbWork* f = ctx->fb;
+    // the sums chain: what the previous call launched; this call has launched
+    // nothing yet, whichever way it returns
+    f->sums_prev = f->sums_now;
+    f->sums_now = false;
     if (!f->done) FBCHK(hipEventCreateWithFlags(&f->done, hipEventDisableTiming), "fb event");
     const int j = f->next;
     f->next = (j + 1) % FbWork::NSCRATCH;
@@ -1944,7 +2146,8 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
         rows.prio = ctx->var[HD_VAR_WAVE_PRIO];
         const int k = split_k_for(ctx, n);
         f->last_k = k;
-#define HD_SPLIT(K, WP) launch_split<K, WP>(ctx, b, d_digest, d_verdict, d_rec32, d_signer, d_bitmap, rows, sc, s, auth, share)
+        const bool overlap = !auth && sums_overlap(ctx, n);
+#define HD_SPLIT(K, WP) launch_split<K, WP>(ctx, b, d_digest, d_verdict, d_rec32, d_signer, d_bitmap, rows, sc, s, auth, share, overlap)
         if (f->wp == HD_FB_WX) {
             if (k == 16) HD_SPLIT(16, HD_FB_WX);
             else HD_SPLIT(8, HD_FB_WX);
@@ -2126,6 +2329,15 @@ int hd_ctx_preimage_stats(hd_ctx* ctx, uint64_t* typed, uint64_t* distinct) {
     FBCHK(hipMemcpy(st, ctx->fb->pstats, 16, hipMemcpyDeviceToHost), "preimage counters read");
     if (typed) *typed = st[0];
     if (distinct) *distinct = st[1];
+    return HD_OK;
+}
+
+int hd_ctx_overlap_stats(hd_ctx* ctx, uint32_t* capped, uint32_t* lean, uint32_t* chained) {
+    if (!ctx) return HD_EINVAL;
+    const FbWork* f = ctx->fb;
+    if (capped) *capped = f ? f->n_capped : 0;
+    if (lean) *lean = f ? f->n_lean : 0;
+    if (chained) *chained = f ? f->n_chained : 0;
     return HD_OK;
 }
 

@@ -257,6 +257,8 @@ int hd_ctx_create(int device, hd_ctx** out) {
         {HD_VAR_KEY_WIDTH, "HD_FB_PW"},           {HD_VAR_WAVE_PRIO, "HD_WAVE_PRIO"},
         {HD_VAR_FOREIGN_KEYS, "HD_FOREIGN_KEYS"}, {HD_VAR_SLOW_LIFT, "HD_SLOW_LIFT"},
         {HD_VAR_DEDUP, "HD_DEDUP"},               {HD_VAR_PRE_SHARE, "HD_PRE_SHARE"},
+        {HD_VAR_SUM_CAP, "HD_SUM_CAP"},           {HD_VAR_SUM_CHAIN, "HD_SUM_CHAIN"},
+        {HD_VAR_LEAN_INV, "HD_LEAN_INV"},
     };
     for (auto& ev : envs)
         if (const char* e = getenv(ev.env)) (void)hd_ctx_set_variant(ctx, ev.key, atoi(e));
@@ -321,6 +323,7 @@ int hd_ctx_set_variant(hd_ctx* ctx, int which, int value) {
         case HD_VAR_SUM_WAVES: ok = value == 0 || (value >= 2 && value <= 4); break;
         case HD_VAR_SUM_PREFETCH: ok = value == 1 || value == 2; break;
         case HD_VAR_RECOVER_G: case HD_VAR_SLOW_LIFT: case HD_VAR_DEDUP: case HD_VAR_PRE_SHARE:
+        case HD_VAR_SUM_CAP: case HD_VAR_SUM_CHAIN: case HD_VAR_LEAN_INV:
             ok = value == 0 || value == 1;
             break;
         case HD_VAR_SPLIT_K: ok = value == -1 || value == 8 || value == 16; break;

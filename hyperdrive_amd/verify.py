@@ -430,8 +430,8 @@ class Verifier:
 
     # include/hd_verify.h HD_VAR_*: kernel variants of this context
     VARIANTS = {"verify_waves": 0, "sum_waves": 1, "sum_prefetch": 2, "split_k": 4, "recover_g": 5,
-                "key_width": 7, "wave_prio": 8, "foreign_keys": 10, "slow_lift": 11, "dedup": 12,
-                "pre_share": 15}
+                "key_width": 7, "wave_prio": 8, "sum_cap": 9, "foreign_keys": 10, "slow_lift": 11,
+                "dedup": 12, "lean_inv": 13, "sum_chain": 14, "pre_share": 15}
 
     def set_variant(self, name: str, value: int) -> None:
         """Select a compiled kernel variant (A/B, variant tests); see
@@ -493,6 +493,15 @@ class Verifier:
         self._check(self._lib.hd_ctx_preimage_stats(self._ctx, ctypes.byref(t), ctypes.byref(d)),
                     "hd_ctx_preimage_stats")
         return int(t.value), int(d.value)
+
+    def overlap_stats(self) -> Tuple[int, int, int]:
+        """(calls with a capped k_fast_sums, calls with the lean inversion
+        kernels, calls whose sums waited for the previous call's), cumulative
+        (include/hd_verify.h hd_ctx_overlap_stats)."""
+        c, l, w = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._lib.hd_ctx_overlap_stats(self._ctx, ctypes.byref(c), ctypes.byref(l), ctypes.byref(w)),
+                    "hd_ctx_overlap_stats")
+        return int(c.value), int(l.value), int(w.value)
 
     def fastpath_geometry(self) -> Tuple[int, int, int]:
         """(G table windows, per-key table windows, messages sharing one

@@ -162,6 +162,13 @@ int hd_ctx_dedup_stats(hd_ctx* ctx, uint64_t* checked, uint64_t* repeats);
  * distinct = the preimages those calls hashed (one SHA-256 each, two blocks
  * for a propose).  Either may be NULL; synchronises the context's calls. */
 int hd_ctx_preimage_stats(hd_ctx* ctx, uint64_t* typed, uint64_t* distinct);
+/* Verify calls that took the overlap path (HD_VAR_SUM_CAP, HD_VAR_LEAN_INV,
+ * HD_VAR_SUM_CHAIN), cumulative since context creation, counted on the host
+ * when the call is submitted: capped = calls whose k_fast_sums was launched
+ * with the LDS reservation, lean = calls that launched the lean inversion
+ * kernels, chained = calls whose k_fast_sums was made to wait for the
+ * previous call's.  Any pointer may be NULL; host-only. */
+int hd_ctx_overlap_stats(hd_ctx* ctx, uint32_t* capped, uint32_t* lean, uint32_t* chained);
 /* Shape of the known-key check as the context runs it now (for cost models):
  * g_windows / key_windows: fixed-base windows of the G table and of the
  * per-key tables (one table point each; the first is loaded, the rest are
@@ -224,10 +231,34 @@ int hd_ctx_profile(hd_ctx* ctx, int enable);
                                    propose) once and every message reads its digest by preimage id; 0 every
                                    message hashes its own (the operator's switch: no adaptive rule)
                                    [HD_PRE_SHARE] */
-/* Keys 3, 6, 9, 13 and 14 (the digit pass, the paired kernel's waves, the
- * sums residency cap, the lean inversions and the sums chain) were measured
+#define HD_VAR_SUM_CAP 9        /* residency of the 3-wave k_fast_sums: 1 (default) a dynamic-LDS reservation
+                                   admits two 256-lane blocks per CU, two waves per SIMD (2 x 168 of 512
+                                   VGPRs), so waves of other calls' short kernels fit beside a running sums;
+                                   0 three waves per SIMD.  The 2- and 4-wave forms are never capped.  On by
+                                   default with keys 13 and 14: the three together measured +2-3 % on 1M C2,
+                                   each alone, cap + chain and cap + lean nothing.  None of the three applies to a call
+                                   that follows one which left more than 1 / 128 of its messages over from
+                                   the known-key check: 30 % adversarial traffic measured 10 % slower with
+                                   them.  The rule reads a count the device writes as earlier calls run, so
+                                   with such calls in flight a call's path (its speed, never its outputs)
+                                   can differ from run to run; hd_ctx_overlap_stats counts the calls that
+                                   took it [HD_SUM_CAP] */
+#define HD_VAR_LEAN_INV 13      /* the two inversion kernels of calls that take the 2- or 3-wave sums: 1
+                                   (default) linear walks whose prefix products go through the rows (97
+                                   VGPRs: a wave fits beside a capped sums); 0 K inputs and prefixes, or a
+                                   product tree, in registers (368 / 397 VGPRs).  Calls that take the 4-wave
+                                   sums (small batches) keep the register forms.  Default and measurement:
+                                   see key 9 [HD_LEAN_INV] */
+#define HD_VAR_SUM_CHAIN 14     /* k_fast_sums of consecutive calls of a context: 1 (default) a call's sums
+                                   waits (on the device) for the previous call's sums when the two calls are
+                                   on different streams, so one call's sums runs at a time and the other
+                                   calls' short kernels run beside it; 0 no such wait.  Calls that take the
+                                   4-wave sums neither wait nor are waited for.  Default and measurement:
+                                   see key 9 [HD_SUM_CHAIN] */
+/* Keys 3 and 6 (the digit pass and the paired kernel's waves) were measured
  * without gain and removed in round 5: set returns HD_EINVAL for them, get
- * returns their fixed value. */
+ * returns their fixed value.  (The cap, the lean inversions and the chain,
+ * removed with them, came back in round 12 under their old keys.) */
 #define HD_VAR__COUNT 16
 int hd_ctx_set_variant(hd_ctx* ctx, int which, int value);
 int hd_ctx_get_variant(hd_ctx* ctx, int which, int* value);
