@@ -42,8 +42,11 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cstddef>
 #include <cstdlib>
+#include <cstring>
 #include <atomic>
+#include <type_traits>
 #include <vector>
 
 #include "hd_internal.h"
@@ -63,15 +66,12 @@ struct TallyWork {
     std::atomic<uint32_t> guess_hr{1024}, guess_cnt{1024};
     // the tables clean themselves (k_tally_emit): cleared only when their
     // allocation or capacity changes, or a call did not queue all its launches
-    bool dirty = false;
-    const void* tab_p = nullptr;
-    uint32_t tab_k = 0;
-    // hd_decide: the propose claim table (cleaned by k_decide_clean) and the
-    // staged row capacity
-    std::atomic<uint32_t> guess_dec{1024};
-    bool pdirty = false;
-    const void* ptab_p = nullptr;
-    uint32_t ptab_k = 0;
+    struct Clean {
+        bool dirty = false;
+        const void* p = nullptr;
+        uint32_t k = 0;
+    } tab, ptab;   // ptab: hd_decide's propose claim table (cleaned by k_decide_clean)
+    std::atomic<uint32_t> guess_dec{1024};   // hd_decide: the staged row capacity
 };
 // T_G: the hash tables and call counters; T_C: the dense log cells; T_D /
 // T_SORTK / T_TMP: a partition's candidate compaction; T_GSLOT / T_DSLOT /
@@ -84,7 +84,7 @@ struct TallyWork {
 // host form's uploaded schedule and value_ok bytes; hd_decide_ordered: T_WKEY /
 // T_WVAL the per-item sort keys and batch indices (unsorted | sorted), T_WTMP
 // the radix sort's temporary storage
-enum TSlot { T_G, T_D, T_C, T_GSLOT, T_DSLOT, T_NSEL, T_SEL, T_SORTK, T_SORTV, T_TMP, T_DUP, T_ROUTE, T_CHECK,
+enum TSlot { T_G, T_D, T_C, T_GSLOT, T_DSLOT, T_NSEL, T_SEL, T_SORTK, T_TMP, T_DUP, T_ROUTE, T_CHECK,
              T_CSLOT, T_BITS, T_P, T_PSLOT, T_DSTAGE, T_DOVF, T_SCHED, T_VOK, T_WKEY, T_WVAL, T_WTMP };
 
 // table layouts (structure of arrays inside one allocation, capacity cap)
@@ -524,20 +524,84 @@ struct TallyCols {
     uint32_t *o_prev, *o_prec, *o_any, *o_rep, *c_rep, *c_n;
     uint8_t* c_t;
 };
+
+// Column tables.  A block of rows at capacity `cap` is a structure of arrays: column after column in the
+// table's order, each width * cap bytes.  One table per row kind names, per column, the kernels' pointer
+// (TallyCols / DecideCols) and the caller's array (hd_tally_out / hd_decide_out), so the layout the kernels
+// write, the row size and every copy out of a block come from one list.
+struct Col {
+    size_t width, dev, out;   // bytes per row; offset of the column's pointer in the kernels' struct, in the out struct
+};
+template <size_t W, size_t WO>
+constexpr Col col_of(size_t dev, size_t out) {
+    static_assert(W == WO, "the kernels' and the caller's column hold the same type");
+    return Col{W, dev, out};
+}
+#define HD_COL(D, d, O, o) col_of<sizeof(*D::d), sizeof(*O::o)>(offsetof(D, d), offsetof(O, o))
+template <size_t N>
+constexpr size_t row_bytes(const Col (&cols)[N]) {
+    size_t b = 0;
+    for (size_t k = 0; k < N; k++) b += cols[k].width;
+    return b;
+}
+// the kernels' pointers of the block at (base, cap), into the struct at x
+template <size_t N>
+HD_HOSTONLY void cols_layout(const Col (&cols)[N], char* base, size_t cap, void* x) {
+    for (const Col& c : cols) {
+        memcpy(static_cast<char*>(x) + c.dev, &base, sizeof base);
+        base += c.width * cap;
+    }
+}
+// `rows` rows of every column of the block at (base, cap) into the caller's arrays of `out`, from row `at`
+// on; a NULL array is skipped.  copy(dst, src, bytes) returns a hipError_t: copy_host from a downloaded
+// stage, copy_down(s) from the overflow block on the device.
+template <size_t N, typename Copy>
+HD_HOSTONLY int cols_copy(hd_ctx* ctx, const Col (&cols)[N], const char* base, size_t cap, size_t rows, size_t at,
+                          const void* out, Copy copy) {
+    for (const Col& c : cols) {
+        char* dst;
+        memcpy(&dst, static_cast<const char*>(out) + c.out, sizeof dst);
+        if (dst && rows)
+            if (hipError_t e = copy(dst + c.width * at, base, c.width * rows)) return hd_ctx_fail(ctx, e, "row copy");
+        base += c.width * cap;
+    }
+    return HD_OK;
+}
+HD_HOSTONLY hipError_t copy_host(void* dst, const void* src, size_t bytes) { return memcpy(dst, src, bytes), hipSuccess; }
+// a download queued on s (the caller synchronises once)
+HD_HOSTONLY auto copy_down(hipStream_t s) {
+    return [s](void* dst, const void* src, size_t n) { return hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, s); };
+}
+HD_HOSTONLY size_t pad64(size_t n) { return (n + 63) & ~(size_t)63; }
+
+// the tally's per-round rows, then its per-value rows at a capacity of their own
+constexpr Col kRoundCols[] = {
+    HD_COL(TallyCols, o_h, hd_tally_out, hr_height),      HD_COL(TallyCols, o_r, hd_tally_out, hr_round),
+    HD_COL(TallyCols, o_prev, hd_tally_out, hr_prevotes), HD_COL(TallyCols, o_prec, hd_tally_out, hr_precommits),
+    HD_COL(TallyCols, o_any, hd_tally_out, hr_any),       HD_COL(TallyCols, o_rep, hd_tally_out, hr_rep),
+};
+constexpr Col kValueCols[] = {
+    HD_COL(TallyCols, c_h, hd_tally_out, count_height), HD_COL(TallyCols, c_r, hd_tally_out, count_round),
+    HD_COL(TallyCols, c_rep, hd_tally_out, count_rep),  HD_COL(TallyCols, c_n, hd_tally_out, count_n),
+    HD_COL(TallyCols, c_t, hd_tally_out, count_type),
+};
+constexpr size_t kRoundRow = row_bytes(kRoundCols), kValueRow = row_bytes(kValueCols);
+static_assert(kRoundRow == 2 * 8 + 4 * 4 && kValueRow == 2 * 8 + 2 * 4 + 1, "tally row bytes");
+static_assert(sizeof(kRoundCols) / sizeof(Col) + sizeof(kValueCols) / sizeof(Col) == sizeof(TallyCols) / sizeof(void*),
+              "every TallyCols pointer is a column of one table");
+
 HD_HOSTONLY TallyCols tally_cols(char* base, uint32_t h, uint32_t c) {
     TallyCols x;
-    x.o_h = reinterpret_cast<int64_t*>(base);
-    x.o_r = x.o_h + h;
-    x.o_prev = reinterpret_cast<uint32_t*>(x.o_r + h);
-    x.o_prec = x.o_prev + h;
-    x.o_any = x.o_prec + h;
-    x.o_rep = x.o_any + h;
-    x.c_h = reinterpret_cast<int64_t*>(base + 32 * (size_t)h);
-    x.c_r = x.c_h + c;
-    x.c_rep = reinterpret_cast<uint32_t*>(x.c_r + c);
-    x.c_n = x.c_rep + c;
-    x.c_t = reinterpret_cast<uint8_t*>(x.c_n + c);
+    cols_layout(kRoundCols, base, h, &x);
+    cols_layout(kValueCols, base + kRoundRow * h, c, &x);
     return x;
+}
+// the rows of such a pair of blocks into out, from rows (at_hr, at_cnt) on
+template <typename Copy>
+HD_HOSTONLY int tally_rows_copy(hd_ctx* ctx, const char* base, uint32_t h, uint32_t c, uint32_t n_hr, uint32_t n_cnt,
+                                uint32_t at_hr, uint32_t at_cnt, const hd_tally_out* out, Copy copy) {
+    if (int rc = cols_copy(ctx, kRoundCols, base, h, n_hr, at_hr, out, copy)) return rc;
+    return cols_copy(ctx, kValueCols, base + kRoundRow * h, c, n_cnt, at_cnt, out, copy);
 }
 
 template <uint32_t IPB>
@@ -967,47 +1031,135 @@ __global__ __launch_bounds__(256) void k_dup_scatter(uint32_t n, const uint8_t* 
     if (j < n) dup_global[gidx[j]] = dup[j];
 }
 
-// The first rows (at most capacities h, c of the column arrays at base) into
-// out's arrays, starting at row (o_hr, o_cnt).
-static void tally_unpack(const char* base, uint32_t h, uint32_t c, uint32_t n_hr, uint32_t n_cnt, hd_tally_out* out,
-                         uint32_t o_hr = 0, uint32_t o_cnt = 0) {
-    const TallyCols x = tally_cols(const_cast<char*>(base), h, c);
-    auto put = [&](void* dst, size_t at, const void* src, size_t sz) {
-        if (dst && sz) memcpy((char*)dst + at, src, sz);
-    };
-    put(out->hr_height, 8 * (size_t)o_hr, x.o_h, 8 * (size_t)n_hr);
-    put(out->hr_round, 8 * (size_t)o_hr, x.o_r, 8 * (size_t)n_hr);
-    put(out->hr_prevotes, 4 * (size_t)o_hr, x.o_prev, 4 * (size_t)n_hr);
-    put(out->hr_precommits, 4 * (size_t)o_hr, x.o_prec, 4 * (size_t)n_hr);
-    put(out->hr_any, 4 * (size_t)o_hr, x.o_any, 4 * (size_t)n_hr);
-    put(out->hr_rep, 4 * (size_t)o_hr, x.o_rep, 4 * (size_t)n_hr);
-    put(out->count_height, 8 * (size_t)o_cnt, x.c_h, 8 * (size_t)n_cnt);
-    put(out->count_round, 8 * (size_t)o_cnt, x.c_r, 8 * (size_t)n_cnt);
-    put(out->count_type, (size_t)o_cnt, x.c_t, (size_t)n_cnt);
-    put(out->count_rep, 4 * (size_t)o_cnt, x.c_rep, 4 * (size_t)n_cnt);
-    put(out->count_n, 4 * (size_t)o_cnt, x.c_n, 4 * (size_t)n_cnt);
+// the stage layout: [n_hr, n_cnt | classification (n bytes, when staged) |
+// per-round rows (kRoundCols, capacity h) | per-value rows (kValueCols, capacity c)]
+static size_t tally_rows_off(uint32_t n, bool dup) { return 64 + pad64(dup ? n : 0); }
+static size_t tally_stage_bytes(uint32_t n, bool dup, uint32_t h, uint32_t c) {
+    return tally_rows_off(n, dup) + kRoundRow * h + kValueRow * c + 64;
 }
 
-// the stage layout: [n_hr, n_cnt | classification (n bytes, when staged) |
-// per-round rows (32 B each, capacity h) | per-value rows (25 B each, capacity c)]
-static size_t tally_rows_off(uint32_t n, bool dup) { return 64 + (((dup ? (size_t)n : 0) + 63) & ~(size_t)63); }
-static size_t tally_stage_bytes(uint32_t n, bool dup, uint32_t h, uint32_t c) {
-    return tally_rows_off(n, dup) + 32 * (size_t)h + 25 * (size_t)c + 64;
+// A call's one download: `bytes` of the device stage into the context's pinned stage (grown with a quarter
+// to spare), and the synchronisation.  Returns the host copy, or NULL with the error in *rc.
+static const char* tally_download(hd_ctx* ctx, const void* d_stage, size_t bytes, hipStream_t s, int* rc) {
+    TallyWork* tw = ctx->tally;
+    hipError_t e = hipSuccess;
+    if (tw->host_cap < bytes) {
+        if (tw->host) (void)hipHostFree(tw->host);
+        tw->host = nullptr;
+        tw->host_cap = 0;
+        e = hipHostMalloc(&tw->host, bytes + (bytes >> 2), hipHostMallocDefault);
+        if (e == hipSuccess) tw->host_cap = bytes + (bytes >> 2);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(tw->host, d_stage, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) return (const char*)tw->host;
+    *rc = hd_ctx_fail(ctx, e, "tally stage download");
+    return nullptr;
+}
+
+// the order passes' run-time items per block as a compile-time one: f(std::integral_constant<uint32_t, IPB>)
+template <typename F>
+static void with_ipb(uint32_t ipb, F f) {
+    switch (ipb) {
+        case 256u: f(std::integral_constant<uint32_t, 256u>{}); break;
+        case 512u: f(std::integral_constant<uint32_t, 512u>{}); break;
+        case 1024u: f(std::integral_constant<uint32_t, 1024u>{}); break;
+        case 2048u: f(std::integral_constant<uint32_t, 2048u>{}); break;
+    }
+}
+
+// The tables and per-item scratch of one call over m items.  The tally, the decide and (through
+// hd_decide_run) the retained log run on the context's one set of buffers and hand each other clean
+// tables, so the sizes, the slicing and the clear are decided here and nowhere else.
+struct TallyPlan {
+    uint32_t grid;        // blocks of the probe passes
+    uint32_t cap, mask;   // slots of each hash table (a power of two), cap - 1
+    uint32_t ipb, nbo;    // items per block and blocks of the order passes
+    uint32_t* tabs;       // the table allocation (the clean check reads it whole)
+    GTab G;
+    CTab C;
+    uint32_t* d;          // the hashed log table D
+    TallyCtr* ctr;        // the call counters, after the tables
+    uint32_t *gslot, *ref, *cslot;             // per item: round slot, log reference, count slot
+    uint32_t *Bg, *Bc, *pre_g, *pre_c, *blk;   // first-item bitmaps, their prefixes, block totals
+    uint32_t S, nd;       // admitted signatories; rounds with dense log cells
+    uint32_t* Dd;         // the dense cells (nd x 2 x S words), NULL without admitted signatories
+    uint32_t *P, *pslot;  // hd_decide: the propose claim table and the per-item propose slot
+};
+
+// Sizes and allocates the plan and queues the clear the tables need.  The kernels leave them clean
+// (k_tally_emit, k_decide_clean), so that is on first use, at a new allocation or capacity, or after a call
+// that did not queue all its launches: the tables count as dirty from here until tally_plan_done.
+// `propose` adds hd_decide's table P, with a clear state of its own.
+static int tally_plan(hd_ctx* ctx, uint32_t m, bool propose, hipStream_t s, TallyPlan& p) {
+    TallyWork* tw = ctx->tally;
+    // blocks per CU of the probe passes (HD_TALLY_BPC, default 16)
+    static const uint32_t bpc = getenv("HD_TALLY_BPC") ? (uint32_t)std::max(1, atoi(getenv("HD_TALLY_BPC"))) : 16u;
+    p = TallyPlan{};
+    p.grid = std::min<uint32_t>(nblk(m), (uint32_t)ctx->n_cu * bpc);
+    // the tables hold at most one key per item, load factor <= 1/2 so probes terminate
+    p.cap = 1024;
+    while (p.cap < 2 * m) p.cap <<= 1;
+    p.mask = p.cap - 1;
+    p.ipb = tally_ipb(m, (uint32_t)ctx->n_cu);
+    p.nbo = (m + p.ipb - 1) / p.ipb;
+    const size_t nw = (size_t)p.nbo * (p.ipb / 32), K = p.cap;
+    int rc = 0;
+    // one allocation for the tables, K words each: the claim words (G, C, D:
+    // empty), the counters (G x 3, C: zero), the round numbers (gid); then the
+    // call counters (TallyCtr)
+    char* tb = (char*)tbuf(ctx, T_G, 4 * 8 * K + sizeof(TallyCtr), &rc);
+    p.gslot = (uint32_t*)tbuf(ctx, T_GSLOT, 4 * (size_t)m, &rc);
+    p.ref = (uint32_t*)tbuf(ctx, T_DSLOT, 4 * (size_t)m, &rc);
+    p.cslot = (uint32_t*)tbuf(ctx, T_CSLOT, 4 * (size_t)m, &rc);
+    // Bg | Bc | pre_g | pre_c (nw words each) | block totals (2 nbo)
+    uint32_t* bits = (uint32_t*)tbuf(ctx, T_BITS, 4 * (4 * nw + 2 * (size_t)p.nbo), &rc);
+    if (propose) {
+        p.P = (uint32_t*)tbuf(ctx, T_P, 4 * K, &rc);
+        p.pslot = (uint32_t*)tbuf(ctx, T_PSLOT, 4 * (size_t)m, &rc);
+    }
+    // dense log cells (nd rounds x 2 x S) for admitted signatories, the hashed
+    // D table for the rest: room for every item's round up to HD_TALLY_DENSE_MAX words
+    p.S = ctx->n_adm;
+    const size_t dcap = p.S > 0 ? std::min<size_t>(HD_TALLY_DENSE_MAX, (size_t)m * 2 * p.S) : 0;
+    p.nd = p.S > 0 ? (uint32_t)(dcap / (2 * (size_t)p.S)) : 0u;
+    p.Dd = dcap ? (uint32_t*)tbuf(ctx, T_C, 4 * dcap, &rc) : nullptr;
+    if (rc) return rc;
+    uint32_t* tabs = p.tabs = (uint32_t*)tb;
+    p.G = GTab{tabs, tabs + 3 * K, tabs + 4 * K, tabs + 5 * K, tabs + 7 * K};
+    p.C = CTab{tabs + K, tabs + 6 * K};
+    p.d = tabs + 2 * K;
+    p.ctr = reinterpret_cast<TallyCtr*>(tb + 4 * 8 * K);
+    p.Bg = bits, p.Bc = bits + nw, p.pre_g = bits + 2 * nw, p.pre_c = bits + 3 * nw, p.blk = bits + 4 * nw;
+    auto stale = [&](const TallyWork::Clean& c, const void* at) { return c.dirty || c.p != at || c.k != p.cap; };
+    if (stale(tw->tab, tb)) {
+        TCHK(hipMemsetAsync(tabs, 0xFF, 4 * 3 * K, s), "clear claims");
+        TCHK(hipMemsetAsync(tabs + 3 * K, 0, 4 * 4 * K, s), "clear counters");
+        TCHK(hipMemsetAsync(p.ctr, 0, sizeof(TallyCtr), s), "clear call counters");
+    }
+    if (propose && stale(tw->ptab, p.P)) TCHK(hipMemsetAsync(p.P, 0xFF, 4 * K, s), "clear propose claims");
+    tw->tab = {true, tb, p.cap};
+    if (propose) tw->ptab = {true, p.P, p.cap};
+    return HD_OK;
+}
+// every launch of the plan's call is queued: its kernels leave the tables clean
+static void tally_plan_done(hd_ctx* ctx, const TallyPlan& p) {
+    ctx->tally->tab.dirty = false;
+    if (p.P) ctx->tally->ptab.dirty = false;
 }
 
 // HD_TALLY_CHECK: the invariants of the tables just built (k_tally_check_*),
 // read back at once (a synchronisation: debug only)
-static int tally_check(hd_ctx* ctx, const DevBatch& b, const uint32_t* cand, uint32_t m, uint32_t cap, GTab G,
-                       CTab C, const uint32_t* D, const uint32_t* Dd, const TallyCtr* ctr, uint32_t per, uint32_t nd,
-                       const uint32_t* gslot, const uint32_t* ref, hipStream_t s) {
+static int tally_check(hd_ctx* ctx, const DevBatch& b, const uint32_t* cand, uint32_t m, const TallyPlan& p,
+                       hipStream_t s) {
     int rc = 0;
     TallyCheck* chk = (TallyCheck*)tbuf(ctx, T_CHECK, sizeof(TallyCheck), &rc);
     if (rc) return rc;
     TCHK(hipMemsetAsync(chk, 0, sizeof(TallyCheck), s), "tally check clear");
-    const uint32_t grid = std::min<uint32_t>(nblk(std::max(m, cap)), (uint32_t)ctx->n_cu * 8u);
-    k_tally_check_items<<<grid, 256, 0, s>>>(m, gslot, ref, Dd, D, chk);
-    k_tally_check_cells<<<grid, 256, 0, s>>>(Dd, ctr, per, nd, m, ref, chk);
-    k_tally_check_slots<<<grid, 256, 0, s>>>(b, cand, m, cap, G, C, D, Dd, gslot, ref, chk);
+    const uint32_t grid = std::min<uint32_t>(nblk(std::max(m, p.cap)), (uint32_t)ctx->n_cu * 8u);
+    k_tally_check_items<<<grid, 256, 0, s>>>(m, p.gslot, p.ref, p.Dd, p.d, chk);
+    k_tally_check_cells<<<grid, 256, 0, s>>>(p.Dd, p.ctr, 2 * p.S, p.nd, m, p.ref, chk);
+    k_tally_check_slots<<<grid, 256, 0, s>>>(b, cand, m, p.cap, p.G, p.C, p.d, p.Dd, p.gslot, p.ref, chk);
     TCHK(hipGetLastError(), "tally check kernels");
     TallyCheck h{};
     TCHK(hipMemcpyAsync(&h, chk, sizeof h, hipMemcpyDeviceToHost, s), "tally check download");
@@ -1019,24 +1171,36 @@ static int tally_check(hd_ctx* ctx, const DevBatch& b, const uint32_t* cand, uin
     snprintf(buf, sizeof buf,
              "tally check failed: winners %u, sum G %u, sum C %u, dense cells %u + D claims %u, stale %u, "
              "bad cells %u, duplicate keys %u, bad C claimers %u (m %u, cap %u)",
-             h.winners, h.sum_g, h.sum_c, h.cells, h.d_claims, h.stale, h.bad_cell, h.dup_key, h.bad_claim, m, cap);
+             h.winners, h.sum_g, h.sum_c, h.cells, h.d_claims, h.stale, h.bad_cell, h.dup_key, h.bad_claim, m, p.cap);
     ctx->last_error = buf;
     return HD_EDEVICE;
 }
 
 // HD_TALLY_CHECK after the emit: every table slot and the counters are clean
-static int tally_check_clean(hd_ctx* ctx, uint32_t cap, const uint32_t* tabs, TallyCtr* ctr, hipStream_t s) {
+static int tally_check_clean(hd_ctx* ctx, const TallyPlan& p, hipStream_t s) {
     int rc = 0;
     uint32_t* bad = (uint32_t*)tbuf(ctx, T_CHECK, sizeof(TallyCheck), &rc);
     if (rc) return rc;
     TCHK(hipMemsetAsync(bad, 0, 4, s), "tally clean check clear");
-    k_tally_check_clean<<<std::min<uint32_t>(nblk(cap), (uint32_t)ctx->n_cu * 8u), 256, 0, s>>>(cap, tabs, ctr, bad);
+    k_tally_check_clean<<<std::min<uint32_t>(nblk(p.cap), (uint32_t)ctx->n_cu * 8u), 256, 0, s>>>(p.cap, p.tabs, p.ctr,
+                                                                                                  bad);
     uint32_t h = 0;
     TCHK(hipMemcpyAsync(&h, bad, 4, hipMemcpyDeviceToHost, s), "tally clean check download");
     TCHK(hipStreamSynchronize(s), "tally clean check sync");
     if (h == 0) return HD_OK;
     ctx->last_error = "tally check failed: " + std::to_string(h) + " table slots not clean after the emit";
     return HD_EDEVICE;
+}
+
+// the device address of an async stage's completion word (word 2), or NULL
+// when the stage is not mapped pinned memory (collect then waits on the event)
+static uint32_t* ticket_signal(void* stage) {
+    void* dp = nullptr;
+    if (hipHostGetDevicePointer(&dp, stage, 0) != hipSuccess || !dp) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    return reinterpret_cast<uint32_t*>(dp) + 2;
 }
 
 // gidx (optional): the batch's messages' global indices -- the rep outputs
@@ -1051,19 +1215,8 @@ static int tally_check_clean(hd_ctx* ctx, uint32_t cap, const uint32_t* tabs, Ta
 // candidate compaction and one host read; a routed owner's scatter one
 // kernel).  The hash tables and counters clean themselves (k_tally_emit), the
 // dense cells are cleared by the round that takes them (k_tally_rounds), and
-// the bitmaps are written whole: nothing is cleared per call unless the
-// table capacity changed or an earlier call did not finish its launches.
-// the device address of an async stage's completion word (word 2), or NULL
-// when the stage is not mapped pinned memory (collect then waits on the event)
-static uint32_t* ticket_signal(void* stage) {
-    void* dp = nullptr;
-    if (hipHostGetDevicePointer(&dp, stage, 0) != hipSuccess || !dp) {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    return reinterpret_cast<uint32_t*>(dp) + 2;
-}
-
+// the bitmaps are written whole: nothing is cleared per call unless
+// tally_plan finds the tables new, resized or left by an unfinished call.
 static int tally_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap,
                         Part part, hd_tally_out* out, hipStream_t s, const uint32_t* gidx = nullptr,
                         uint8_t* dup_global = nullptr, hd_tally_ticket* tk = nullptr) {
@@ -1071,34 +1224,30 @@ static int tally_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdic
     if (!ctx->tally) ctx->tally = new TallyWork();
     DevBatch b{n, hb->type, hb->height, hb->round, hb->valid_round, hb->value32, hb->from32, hb->sig65};
     int rc = 0;
-    // blocks per CU of the probe passes (HD_TALLY_BPC, default 16)
-    static const uint32_t bpc = getenv("HD_TALLY_BPC") ? (uint32_t)std::max(1, atoi(getenv("HD_TALLY_BPC"))) : 16u;
     const bool check = [] {
         const char* e = getenv("HD_TALLY_CHECK");
         return e && atoi(e) != 0;
     }();
-    // The output stage: [n_hr, n_cnt | per-message classification | per-round
-    // rows (32 B each, capacity H) | per-value rows (25 B each, capacity Cg)],
-    // downloaded with ONE copy after ONE host sync.  H and Cg are the previous
-    // call's counts plus a margin; rows past them land in overflow columns on
-    // the device, downloaded by a second round of copies when needed.
+    // The output stage (tally_stage_bytes) is downloaded with ONE copy after
+    // ONE host sync.  Its row capacities H and Cg are the previous call's
+    // counts plus a margin; rows past them land in overflow columns on the
+    // device, downloaded by a second round of copies when needed.
     TallyWork* tw = ctx->tally;
     // the classification is staged for download only when the caller reads it
     // (out->dup, or the ticket's dup); a routed owner's scatter (dup_global)
     // keeps it in device scratch of its own
     const bool stage_dup = tk ? tk->dup != 0 : out->dup != nullptr;
-    const size_t dup_off = 64, rows_off = tally_rows_off(n, stage_dup);
-    uint32_t H = tw->guess_hr, Cg = tw->guess_cnt;
-    auto stage_bytes = [&](uint32_t h, uint32_t c) { return tally_stage_bytes(n, stage_dup, h, c); };
+    const uint32_t H = tw->guess_hr, Cg = tw->guess_cnt;
+    const size_t dup_off = 64, rows_off = tally_rows_off(n, stage_dup), total = tally_stage_bytes(n, stage_dup, H, Cg);
     if (tk) {
         if (part.nparts != 1 || gidx || dup_global) return HD_EINVAL;
         tk->n = n;
         tk->H = H;
         tk->Cg = Cg;
-        tk->need = stage_bytes(H, Cg);
+        tk->need = total;
         if (!tk->stage || tk->stage_cap < tk->need) return HD_ECAP;
     }
-    char* st = (char*)tbuf(ctx, T_SEL, stage_bytes(H, Cg), &rc);
+    char* st = (char*)tbuf(ctx, T_SEL, total, &rc);
     uint8_t* d_dup = stage_dup ? (uint8_t*)(st + dup_off) : nullptr;
     if (!stage_dup && dup_global) d_dup = (uint8_t*)tbuf(ctx, T_DUP, n, &rc);
     if (rc) return rc;
@@ -1129,81 +1278,31 @@ static int tally_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdic
         if (out->dup) memset(out->dup, 3, n);
         return HD_OK;
     }
-    const uint32_t grid = std::min<uint32_t>(nblk(m), (uint32_t)ctx->n_cu * bpc);
-    // the tables hold at most one key per item, load factor <= 1/2 so probes
-    // terminate
-    uint32_t cap = 1024;
-    while (cap < 2 * m) cap <<= 1;
-    const uint32_t mask = cap - 1;
-    const uint32_t ipb = tally_ipb(m, (uint32_t)ctx->n_cu);
-    const uint32_t nbo = (m + ipb - 1) / ipb;   // blocks of the order passes
-    const size_t nw = (size_t)nbo * (ipb / 32);
-    // one allocation for the tables: the claim words (G, C, D: empty), the
-    // counters (G x 3, C: zero), the round numbers (gid); then the call
-    // counters (TallyCtr)
-    const size_t K = cap;
-    char* tb = (char*)tbuf(ctx, T_G, 4 * 8 * K + sizeof(TallyCtr), &rc);
-    uint32_t* gslot = (uint32_t*)tbuf(ctx, T_GSLOT, 4 * (size_t)m, &rc);
-    uint32_t* ref = (uint32_t*)tbuf(ctx, T_DSLOT, 4 * (size_t)m, &rc);
-    uint32_t* cslot = (uint32_t*)tbuf(ctx, T_CSLOT, 4 * (size_t)m, &rc);
-    // Bg | Bc | pre_g | pre_c (nw words each) | block totals (2 nbo)
-    uint32_t* bits = (uint32_t*)tbuf(ctx, T_BITS, 4 * (4 * nw + 2 * (size_t)nbo), &rc);
-    // dense log cells (nd rounds x 2 x S) for admitted signatories, the hashed
-    // D table for the rest: room for every item's round up to HD_TALLY_DENSE_MAX words
-    const uint32_t S = ctx->n_adm;
-    const size_t dcap = S > 0 ? std::min<size_t>(HD_TALLY_DENSE_MAX, (size_t)m * 2 * S) : 0;
-    const uint32_t nd = S > 0 ? (uint32_t)(dcap / (2 * (size_t)S)) : 0u;
-    uint32_t* Dd = dcap ? (uint32_t*)tbuf(ctx, T_C, 4 * dcap, &rc) : nullptr;
-    if (rc) return rc;
-    uint32_t* tabs = (uint32_t*)tb;
-    GTab G{tabs, tabs + 3 * K, tabs + 4 * K, tabs + 5 * K, tabs + 7 * K};
-    CTab C{tabs + K, tabs + 6 * K};
-    uint32_t* d = tabs + 2 * K;
-    TallyCtr* ctr = reinterpret_cast<TallyCtr*>(tb + 4 * 8 * K);
-    if (tw->dirty || tw->tab_p != tb || tw->tab_k != cap) {   // first use, new capacity, or an unfinished call
-        TCHK(hipMemsetAsync(tabs, 0xFF, 4 * 3 * K, s), "clear claims");
-        TCHK(hipMemsetAsync(tabs + 3 * K, 0, 4 * 4 * K, s), "clear counters");
-        TCHK(hipMemsetAsync(ctr, 0, sizeof(TallyCtr), s), "clear call counters");
-        tw->tab_p = tb;
-        tw->tab_k = cap;
-    }
-    tw->dirty = true;   // until every launch below is queued
-    k_tally_rounds<<<grid, 256, 0, s>>>(b, cand, m, d_verdict, d_bitmap, part, G, mask, gslot, d_dup, ctr, Dd, 2 * S,
-                                        nd);
-    k_tally_logs<<<grid, 256, 0, s>>>(b, cand, m, gslot, G.gid, hd_adm_index(ctx), S, Dd, nd, d, mask, ref);
-    k_tally_values<<<grid, 256, 0, s>>>(b, cand, m, Dd, S, d, G, C, mask, gslot, ref, cslot, d_dup);
+    TallyPlan p;
+    if ((rc = tally_plan(ctx, m, false, s, p))) return rc;
+    k_tally_rounds<<<p.grid, 256, 0, s>>>(b, cand, m, d_verdict, d_bitmap, part, p.G, p.mask, p.gslot, d_dup, p.ctr,
+                                          p.Dd, 2 * p.S, p.nd);
+    k_tally_logs<<<p.grid, 256, 0, s>>>(b, cand, m, p.gslot, p.G.gid, hd_adm_index(ctx), p.S, p.Dd, p.nd, p.d, p.mask,
+                                        p.ref);
+    k_tally_values<<<p.grid, 256, 0, s>>>(b, cand, m, p.Dd, p.S, p.d, p.G, p.C, p.mask, p.gslot, p.ref, p.cslot, d_dup);
     if (dup_global && gidx) k_dup_scatter<<<nblk(n), 256, 0, s>>>(n, d_dup, gidx, dup_global);
     TCHK(hipGetLastError(), "tally kernels");
-    if (check) {
-        rc = tally_check(ctx, b, cand, m, cap, G, C, d, Dd, ctr, 2 * S, nd, gslot, ref, s);
-        if (rc) return rc;
-    }
-    uint32_t *Bg = bits, *Bc = bits + nw, *pre_g = bits + 2 * nw, *pre_c = bits + 3 * nw, *blk = bits + 4 * nw;
+    if (check && (rc = tally_check(ctx, b, cand, m, p, s))) return rc;
     // rows at capacity (H, Cg) in the stage, the rest in the overflow columns
     // (capacity m each: a batch has at most m groups of either kind)
-    char* ovf = (char*)tbuf(ctx, T_NSEL, 57 * (size_t)m + 64, &rc);
+    char* ovf = (char*)tbuf(ctx, T_NSEL, (kRoundRow + kValueRow) * m + 64, &rc);
     if (rc) return rc;
     const TallyCols sc = tally_cols(st + rows_off, H, Cg), oc = tally_cols(ovf, m, m);
-    switch (ipb) {
-#define HD_TALLY_ORDER(IPB)                                                                                         \
-    case IPB:                                                                                                       \
-        k_tally_firsts<IPB><<<nbo, 256, 0, s>>>(m, gslot, cslot, G.claim, C.claim, Bg, Bc, pre_g, pre_c, blk);       \
-        k_tally_emit<IPB><<<nbo, 256, 0, s>>>(b, cand, m, gidx, gslot, cslot, ref, G, C, d, Bg, Bc, pre_g, pre_c, blk, \
-                                              sc, H, Cg, oc, ctr, (uint32_t*)st);                                   \
-        break;
-        HD_TALLY_ORDER(256u)
-        HD_TALLY_ORDER(512u)
-        HD_TALLY_ORDER(1024u)
-        HD_TALLY_ORDER(2048u)
-#undef HD_TALLY_ORDER
-    }
+    with_ipb(p.ipb, [&](auto ipb) {
+        constexpr uint32_t IPB = decltype(ipb)::value;
+        k_tally_firsts<IPB><<<p.nbo, 256, 0, s>>>(m, p.gslot, p.cslot, p.G.claim, p.C.claim, p.Bg, p.Bc, p.pre_g,
+                                                  p.pre_c, p.blk);
+        k_tally_emit<IPB><<<p.nbo, 256, 0, s>>>(b, cand, m, gidx, p.gslot, p.cslot, p.ref, p.G, p.C, p.d, p.Bg, p.Bc,
+                                                p.pre_g, p.pre_c, p.blk, sc, H, Cg, oc, p.ctr, (uint32_t*)st);
+    });
     TCHK(hipGetLastError(), "tally order kernels");
-    tw->dirty = false;
-    if (check) {
-        rc = tally_check_clean(ctx, cap, tabs, ctr, s);
-        if (rc) return rc;
-    }
-    const size_t total = stage_bytes(H, Cg);
+    tally_plan_done(ctx, p);
+    if (check && (rc = tally_check_clean(ctx, p, s))) return rc;
     if (tk) {   // queued; hd_tally_collect waits for the signal (or tk->done), then reads the stage
         // the completion word restarts at 0 (the stage's previous ticket was collected)
         reinterpret_cast<volatile uint32_t*>(tk->stage)[2] = 0u;
@@ -1213,45 +1312,20 @@ static int tally_device(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdic
         TCHK(hipEventRecord((hipEvent_t)tk->done, s), "tally event record");
         return hd_ctx_note_stream(ctx, s);
     }
-    if (tw->host_cap < total) {
-        if (tw->host) (void)hipHostFree(tw->host);
-        tw->host = nullptr;
-        tw->host_cap = 0;
-        TCHK(hipHostMalloc(&tw->host, total + (total >> 2), hipHostMallocDefault), "tally host stage");
-        tw->host_cap = total + (total >> 2);
-    }
-    TCHK(hipMemcpyAsync(tw->host, st, total, hipMemcpyDeviceToHost, s), "tally download");
-    TCHK(hipStreamSynchronize(s), "tally sync");
-    const uint32_t n_hr = reinterpret_cast<const uint32_t*>(tw->host)[0];
-    const uint32_t n_cnt = reinterpret_cast<const uint32_t*>(tw->host)[1];
+    const char* hs = tally_download(ctx, st, total, s, &rc);
+    if (!hs) return rc;
+    const uint32_t n_hr = reinterpret_cast<const uint32_t*>(hs)[0];
+    const uint32_t n_cnt = reinterpret_cast<const uint32_t*>(hs)[1];
     out->n_hr = n_hr;
     out->n_counts = n_cnt;
     tw->guess_hr = std::max<uint32_t>(1024u, n_hr + n_hr / 4);
     tw->guess_cnt = std::max<uint32_t>(1024u, n_cnt + n_cnt / 4);
     if (n_hr > out->cap_hr || n_cnt > out->cap_counts) return HD_ECAP;
-    if (out->dup) memcpy(out->dup, (const char*)tw->host + dup_off, (size_t)n);
-    tally_unpack((const char*)tw->host + rows_off, H, Cg, std::min(n_hr, H), std::min(n_cnt, Cg), out);
+    if (out->dup) memcpy(out->dup, hs + dup_off, (size_t)n);
+    (void)tally_rows_copy(ctx, hs + rows_off, H, Cg, std::min(n_hr, H), std::min(n_cnt, Cg), 0, 0, out, copy_host);
     if (n_hr > H || n_cnt > Cg) {   // more groups than staged: the overflow columns, straight into out
         const uint32_t eh = n_hr > H ? n_hr - H : 0, ec = n_cnt > Cg ? n_cnt - Cg : 0;
-        struct Piece {
-            void* dst;
-            const void* src;
-            size_t sz;
-        } pieces[] = {
-            {out->hr_height ? out->hr_height + H : nullptr, oc.o_h, 8 * (size_t)eh},
-            {out->hr_round ? out->hr_round + H : nullptr, oc.o_r, 8 * (size_t)eh},
-            {out->hr_prevotes ? out->hr_prevotes + H : nullptr, oc.o_prev, 4 * (size_t)eh},
-            {out->hr_precommits ? out->hr_precommits + H : nullptr, oc.o_prec, 4 * (size_t)eh},
-            {out->hr_any ? out->hr_any + H : nullptr, oc.o_any, 4 * (size_t)eh},
-            {out->hr_rep ? out->hr_rep + H : nullptr, oc.o_rep, 4 * (size_t)eh},
-            {out->count_height ? out->count_height + Cg : nullptr, oc.c_h, 8 * (size_t)ec},
-            {out->count_round ? out->count_round + Cg : nullptr, oc.c_r, 8 * (size_t)ec},
-            {out->count_type ? out->count_type + Cg : nullptr, oc.c_t, (size_t)ec},
-            {out->count_rep ? out->count_rep + Cg : nullptr, oc.c_rep, 4 * (size_t)ec},
-            {out->count_n ? out->count_n + Cg : nullptr, oc.c_n, 4 * (size_t)ec},
-        };
-        for (const Piece& p : pieces)
-            if (p.dst && p.sz) TCHK(hipMemcpyAsync(p.dst, p.src, p.sz, hipMemcpyDeviceToHost, s), "tally overflow");
+        if ((rc = tally_rows_copy(ctx, ovf, m, m, eh, ec, H, Cg, out, copy_down(s)))) return rc;
         TCHK(hipStreamSynchronize(s), "tally overflow sync");
     }
     return HD_OK;
@@ -1375,8 +1449,8 @@ int hd_tally_collect(hd_ctx* ctx, const hd_tally_ticket* ticket, hd_tally_out* o
         if (!ticket->dup) return HD_EINVAL;
         memcpy(out->dup, st + 64, (size_t)ticket->n);
     }
-    tally_unpack(st + tally_rows_off(ticket->n, ticket->dup != 0), ticket->H, ticket->Cg, n_hr, n_cnt, out);
-    return HD_OK;
+    return tally_rows_copy(ctx, st + tally_rows_off(ticket->n, ticket->dup != 0), ticket->H, ticket->Cg, n_hr, n_cnt, 0, 0,
+                           out, copy_host);
 }
 
 int hd_tally_device_bitmap_part(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap, uint32_t part,
@@ -1551,22 +1625,21 @@ struct DecideCols {
     uint32_t *rep, *propose, *prevotes, *precommits, *trace, *pv_value, *pc_value, *pv_nil, *pv_validround;
     uint8_t *flags, *bits;
 };
-#define HD_DECIDE_ROW_BYTES 54u   // 2 x 8 + 9 x 4 + 2
+#define HD_DCOL(f) HD_COL(DecideCols, f, hd_decide_out, f)
+constexpr Col kDecideCols[] = {
+    HD_COL(DecideCols, h, hd_decide_out, height), HD_COL(DecideCols, r, hd_decide_out, round),
+    HD_DCOL(rep), HD_DCOL(propose), HD_DCOL(prevotes), HD_DCOL(precommits), HD_DCOL(trace), HD_DCOL(pv_value),
+    HD_DCOL(pc_value), HD_DCOL(pv_nil), HD_DCOL(pv_validround), HD_DCOL(flags), HD_DCOL(bits),
+};
+constexpr size_t kDecideRow = row_bytes(kDecideCols);
+static_assert(kDecideRow == 2 * 8 + 9 * 4 + 2, "decide row bytes");
+static_assert(sizeof(kDecideCols) / sizeof(Col) == sizeof(DecideCols) / sizeof(void*), "every DecideCols pointer is a column");
+// the ordered form's rows, after the decide rows at strides of their own
+constexpr size_t kWhenRow = 8 * sizeof(uint32_t), kUntilRow = sizeof(uint32_t);
+
 HD_HOSTONLY DecideCols decide_cols(char* base, uint32_t cap) {
     DecideCols x;
-    x.h = reinterpret_cast<int64_t*>(base);
-    x.r = x.h + cap;
-    x.rep = reinterpret_cast<uint32_t*>(x.r + cap);
-    x.propose = x.rep + cap;
-    x.prevotes = x.propose + cap;
-    x.precommits = x.prevotes + cap;
-    x.trace = x.precommits + cap;
-    x.pv_value = x.trace + cap;
-    x.pc_value = x.pv_value + cap;
-    x.pv_nil = x.pc_value + cap;
-    x.pv_validround = x.pv_nil + cap;
-    x.flags = reinterpret_cast<uint8_t*>(x.pv_validround + cap);
-    x.bits = x.flags + cap;
+    cols_layout(kDecideCols, base, cap, &x);
     return x;
 }
 
@@ -2061,8 +2134,6 @@ __global__ __launch_bounds__(256) void k_decide_when(DevBatch b, uint32_t m, Dec
     }
 }
 
-static size_t decide_pad(size_t n) { return (n + 63) & ~(size_t)63; }
-
 static bool decide_out_ok(const hd_decide_out* o) {
     return o && o->height && o->round && o->rep && o->propose && o->prevotes && o->precommits && o->trace &&
            o->pv_value && o->pc_value && o->pv_nil && o->pv_validround && o->flags && o->bits;
@@ -2072,19 +2143,6 @@ static bool decide_out_ok(const hd_decide_out* o) {
 // for flags, so a batch has fewer than 2^30 messages
 static bool decide_order_ok(const hd_decide_out* o, const hd_decide_order* w, uint32_t n) {
     return o && w && w->when && w->exact_until && w->cap >= o->cap && n < (1u << 30);
-}
-
-static void decide_unpack(const DecideCols& x, uint32_t rows, uint32_t at, hd_decide_out* out) {
-    if (!rows) return;
-    memcpy(out->height + at, x.h, 8 * (size_t)rows);
-    memcpy(out->round + at, x.r, 8 * (size_t)rows);
-    uint32_t* const dst[] = {out->rep, out->propose, out->prevotes, out->precommits, out->trace,
-                             out->pv_value, out->pc_value, out->pv_nil, out->pv_validround};
-    const uint32_t* const src[] = {x.rep, x.propose, x.prevotes, x.precommits, x.trace,
-                                   x.pv_value, x.pc_value, x.pv_nil, x.pv_validround};
-    for (int k = 0; k < 9; k++) memcpy(dst[k] + at, src[k], 4 * (size_t)rows);
-    memcpy(out->flags + at, x.flags, rows);
-    memcpy(out->bits + at, x.bits, rows);
 }
 
 // Whole batch only (items = batch indices).  One download of the stage
@@ -2100,40 +2158,19 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
     if (!ctx->tally) ctx->tally = new TallyWork();
     TallyWork* tw = ctx->tally;
     DevBatch b{n, hb->type, hb->height, hb->round, hb->valid_round, hb->value32, hb->from32, nullptr};
-    static const uint32_t bpc = getenv("HD_TALLY_BPC") ? (uint32_t)std::max(1, atoi(getenv("HD_TALLY_BPC"))) : 16u;
     int rc = 0;
     const uint32_t H = tw->guess_dec;
     const bool st_dup = !ext && out->dup, st_pclass = !ext && out->pclass;   // staged and downloaded
-    const size_t dup_off = 64, pc_off = dup_off + (st_dup ? decide_pad(n) : 0),
-                 rows_off = pc_off + (st_pclass ? decide_pad(n) : 0);
-    const size_t when_off = rows_off + decide_pad(HD_DECIDE_ROW_BYTES * (size_t)H), until_off = when_off + 32 * (size_t)H;
-    const size_t total = ord ? until_off + 4 * (size_t)H + 64 : rows_off + HD_DECIDE_ROW_BYTES * (size_t)H + 64;
+    const size_t dup_off = 64, pc_off = dup_off + (st_dup ? pad64(n) : 0), rows_off = pc_off + (st_pclass ? pad64(n) : 0);
+    const size_t when_off = rows_off + pad64(kDecideRow * H), until_off = when_off + kWhenRow * H;
+    const size_t total = ord ? until_off + kUntilRow * H + 64 : rows_off + kDecideRow * H + 64;
     char* st = (char*)tbuf(ctx, T_DSTAGE, total, &rc);
     if (rc) return rc;
     uint8_t* d_dup = ext ? ext->d_dup : st_dup ? (uint8_t*)(st + dup_off) : nullptr;
     uint8_t* d_pclass = ext ? ext->d_pclass : st_pclass ? (uint8_t*)(st + pc_off) : nullptr;
-    const uint32_t grid = std::min<uint32_t>(nblk(m), (uint32_t)ctx->n_cu * bpc);
-    uint32_t cap = 1024;
-    while (cap < 2 * m) cap <<= 1;
-    const uint32_t mask = cap - 1;
-    const uint32_t ipb = tally_ipb(m, (uint32_t)ctx->n_cu);
-    const uint32_t nbo = (m + ipb - 1) / ipb;
-    const size_t nw = (size_t)nbo * (ipb / 32);
-    const size_t K = cap;
-    // the tally's tables, scratch and dense cells, laid out exactly as tally_device does
-    char* tb = (char*)tbuf(ctx, T_G, 4 * 8 * K + sizeof(TallyCtr), &rc);
-    uint32_t* gslot = (uint32_t*)tbuf(ctx, T_GSLOT, 4 * (size_t)m, &rc);
-    uint32_t* ref = (uint32_t*)tbuf(ctx, T_DSLOT, 4 * (size_t)m, &rc);
-    uint32_t* cslot = (uint32_t*)tbuf(ctx, T_CSLOT, 4 * (size_t)m, &rc);
-    uint32_t* bits = (uint32_t*)tbuf(ctx, T_BITS, 4 * (4 * nw + 2 * (size_t)nbo), &rc);
-    uint32_t* P = (uint32_t*)tbuf(ctx, T_P, 4 * K, &rc);
-    uint32_t* pslot = (uint32_t*)tbuf(ctx, T_PSLOT, 4 * (size_t)m, &rc);
-    const size_t ovw_off = decide_pad(HD_DECIDE_ROW_BYTES * (size_t)m + 64), ovu_off = ovw_off + 32 * (size_t)m;
-    char* ovf = (char*)tbuf(ctx, T_DOVF, ord ? ovu_off + 4 * (size_t)m + 64 : HD_DECIDE_ROW_BYTES * (size_t)m + 64, &rc);
-    const uint32_t S = ctx->n_adm;
-    const size_t dcap = S > 0 ? std::min<size_t>(HD_TALLY_DENSE_MAX, (size_t)m * 2 * S) : 0;
-    const uint32_t nd = S > 0 ? (uint32_t)(dcap / (2 * (size_t)S)) : 0u;
-    uint32_t* Dd = dcap ? (uint32_t*)tbuf(ctx, T_C, 4 * dcap, &rc) : nullptr;
+    // the overflow rows (capacity m), the ordered form's after them
+    const size_t ovw_off = pad64(kDecideRow * m + 64), ovu_off = ovw_off + kWhenRow * m;
+    char* ovf = (char*)tbuf(ctx, T_DOVF, ord ? ovu_off + kUntilRow * m + 64 : kDecideRow * m + 64, &rc);
     // the ordered form's sort: keys over the bits that hold every round number and, above them, the
     // key of the items that are no logged vote
     uint32_t *wkey = nullptr, *wval = nullptr, kbits = 1;
@@ -2150,109 +2187,67 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
         wtmp = tbuf(ctx, T_WTMP, wtmp_bytes + 64, &rc);
     }
     if (rc) return rc;
-    uint32_t* tabs = (uint32_t*)tb;
-    GTab G{tabs, tabs + 3 * K, tabs + 4 * K, tabs + 5 * K, tabs + 7 * K};
-    CTab C{tabs + K, tabs + 6 * K};
-    uint32_t* d = tabs + 2 * K;
-    TallyCtr* ctr = reinterpret_cast<TallyCtr*>(tb + 4 * 8 * K);
-    if (tw->dirty || tw->tab_p != tb || tw->tab_k != cap) {
-        TCHK(hipMemsetAsync(tabs, 0xFF, 4 * 3 * K, s), "clear claims");
-        TCHK(hipMemsetAsync(tabs + 3 * K, 0, 4 * 4 * K, s), "clear counters");
-        TCHK(hipMemsetAsync(ctr, 0, sizeof(TallyCtr), s), "clear call counters");
-        tw->tab_p = tb;
-        tw->tab_k = cap;
-    }
-    if (tw->pdirty || tw->ptab_p != P || tw->ptab_k != cap) {
-        TCHK(hipMemsetAsync(P, 0xFF, 4 * K, s), "clear propose claims");
-        tw->ptab_p = P;
-        tw->ptab_k = cap;
-    }
-    tw->dirty = tw->pdirty = true;   // until every launch below is queued
+    TallyPlan p;
+    if ((rc = tally_plan(ctx, m, true, s, p))) return rc;
     const AdmIndex ix = hd_adm_index(ctx);
-    k_decide_claim<<<grid, 256, 0, s>>>(b, d_verdict, d_bitmap, in, P, mask, pslot, d_pclass);
-    k_tally_rounds<<<grid, 256, 0, s>>>(b, nullptr, m, d_verdict, d_bitmap, Part{0, 1}, G, mask, gslot, d_dup, ctr, Dd,
-                                        2 * S, nd);
-    k_tally_logs<<<grid, 256, 0, s>>>(b, nullptr, m, gslot, G.gid, ix, S, Dd, nd, d, mask, ref);
-    k_tally_values<<<grid, 256, 0, s>>>(b, nullptr, m, Dd, S, d, G, C, mask, gslot, ref, cslot, d_dup);
-    k_decide_log<<<grid, 256, 0, s>>>(b, P, pslot, G, mask, gslot, cslot, ref, d_pclass);
+    k_decide_claim<<<p.grid, 256, 0, s>>>(b, d_verdict, d_bitmap, in, p.P, p.mask, p.pslot, d_pclass);
+    k_tally_rounds<<<p.grid, 256, 0, s>>>(b, nullptr, m, d_verdict, d_bitmap, Part{0, 1}, p.G, p.mask, p.gslot, d_dup,
+                                          p.ctr, p.Dd, 2 * p.S, p.nd);
+    k_tally_logs<<<p.grid, 256, 0, s>>>(b, nullptr, m, p.gslot, p.G.gid, ix, p.S, p.Dd, p.nd, p.d, p.mask, p.ref);
+    k_tally_values<<<p.grid, 256, 0, s>>>(b, nullptr, m, p.Dd, p.S, p.d, p.G, p.C, p.mask, p.gslot, p.ref, p.cslot,
+                                          d_dup);
+    k_decide_log<<<p.grid, 256, 0, s>>>(b, p.P, p.pslot, p.G, p.mask, p.gslot, p.cslot, p.ref, d_pclass);
     TCHK(hipGetLastError(), "decide kernels");
-    uint32_t *Bg = bits, *Bc = bits + nw, *pre_g = bits + 2 * nw, *pre_c = bits + 3 * nw, *blk = bits + 4 * nw;
     const DecideCols sc = decide_cols(st + rows_off, H), oc = decide_cols(ovf, m);
-    switch (ipb) {
-#define HD_DECIDE_ORDER(IPB)                                                                                     \
-    case IPB:                                                                                                    \
-        k_tally_firsts<IPB><<<nbo, 256, 0, s>>>(m, gslot, cslot, G.claim, C.claim, Bg, Bc, pre_g, pre_c, blk);    \
-        k_decide_emit<IPB><<<nbo, 256, 0, s>>>(b, m, in, gslot, G, C, d, P, Dd, ix, S, nd, mask, Bg, pre_g, blk,  \
-                                               sc, H, oc, (uint32_t*)st);                                        \
-        break;
-        HD_DECIDE_ORDER(256u)
-        HD_DECIDE_ORDER(512u)
-        HD_DECIDE_ORDER(1024u)
-        HD_DECIDE_ORDER(2048u)
-#undef HD_DECIDE_ORDER
-    }
+    with_ipb(p.ipb, [&](auto ipb) {
+        constexpr uint32_t IPB = decltype(ipb)::value;
+        k_tally_firsts<IPB><<<p.nbo, 256, 0, s>>>(m, p.gslot, p.cslot, p.G.claim, p.C.claim, p.Bg, p.Bc, p.pre_g,
+                                                  p.pre_c, p.blk);
+        k_decide_emit<IPB><<<p.nbo, 256, 0, s>>>(b, m, in, p.gslot, p.G, p.C, p.d, p.P, p.Dd, ix, p.S, p.nd, p.mask,
+                                                 p.Bg, p.pre_g, p.blk, sc, H, oc, (uint32_t*)st);
+    });
     if (ord) {   // between the emit and the clean: the tables are populated and read-only
         const uint32_t kmask = (uint32_t)((1ull << kbits) - 1ull);
-        k_decide_order_keys<<<grid, 256, 0, s>>>(b, m, gslot, cslot, ref, G.gid, Dd, S, d, mask, kmask, wkey, wval);
+        k_decide_order_keys<<<p.grid, 256, 0, s>>>(b, m, p.gslot, p.cslot, p.ref, p.G.gid, p.Dd, p.S, p.d, p.mask,
+                                                   kmask, wkey, wval);
         TCHK(hipGetLastError(), "decide order keys");
         TCHK(hipcub::DeviceRadixSort::SortPairs(wtmp, wtmp_bytes, wkey, wkey + m, wval, wval + m, (int)m, 0,
                                                 (int)kbits, s),
              "decide sort");
         const uint32_t wgrid = std::min<uint32_t>((m + 3) / 4, (uint32_t)ctx->n_cu * 8u);   // four rows per block
-        k_decide_when<<<wgrid, 256, 0, s>>>(b, m, in, gslot, cslot, G, C, d, Dd, ix, S, nd, mask, wkey + m, wval + m,
-                                            kmask, sc, H, oc, (const uint32_t*)st, (uint32_t*)(st + when_off),
-                                            (uint32_t*)(st + until_off), (uint32_t*)(ovf + ovw_off),
-                                            (uint32_t*)(ovf + ovu_off));
+        k_decide_when<<<wgrid, 256, 0, s>>>(b, m, in, p.gslot, p.cslot, p.G, p.C, p.d, p.Dd, ix, p.S, p.nd, p.mask,
+                                            wkey + m, wval + m, kmask, sc, H, oc, (const uint32_t*)st,
+                                            (uint32_t*)(st + when_off), (uint32_t*)(st + until_off),
+                                            (uint32_t*)(ovf + ovw_off), (uint32_t*)(ovf + ovu_off));
     }
-    k_decide_clean<<<grid, 256, 0, s>>>(m, gslot, cslot, ref, pslot, G, C, d, P, Bg, ctr);
+    k_decide_clean<<<p.grid, 256, 0, s>>>(m, p.gslot, p.cslot, p.ref, p.pslot, p.G, p.C, p.d, p.P, p.Bg, p.ctr);
     TCHK(hipGetLastError(), "decide order kernels");
-    tw->dirty = tw->pdirty = false;
+    tally_plan_done(ctx, p);
     if (ext && ext->queued) {
         rc = ext->queued(ext->arg, s);
         if (rc) return rc;
     }
-    if (tw->host_cap < total) {
-        if (tw->host) (void)hipHostFree(tw->host);
-        tw->host = nullptr;
-        tw->host_cap = 0;
-        TCHK(hipHostMalloc(&tw->host, total + (total >> 2), hipHostMallocDefault), "decide host stage");
-        tw->host_cap = total + (total >> 2);
-    }
-    TCHK(hipMemcpyAsync(tw->host, st, total, hipMemcpyDeviceToHost, s), "decide download");
-    TCHK(hipStreamSynchronize(s), "decide sync");
-    const char* hs = (const char*)tw->host;
+    const char* hs = tally_download(ctx, st, total, s, &rc);
+    if (!hs) return rc;
     const uint32_t rows = reinterpret_cast<const uint32_t*>(hs)[0];
     out->n = rows;
     tw->guess_dec = std::max<uint32_t>(1024u, rows + rows / 4);
     if (rows > out->cap) return HD_ECAP;
     if (st_dup) memcpy(out->dup, hs + dup_off, n);
     if (st_pclass) memcpy(out->pclass, hs + pc_off, n);
-    decide_unpack(decide_cols(const_cast<char*>(hs) + rows_off, H), std::min(rows, H), 0, out);
+    const uint32_t staged = std::min(rows, H);
+    (void)cols_copy(ctx, kDecideCols, hs + rows_off, H, staged, 0, out, copy_host);
     if (ord) {
-        memcpy(ord->when, hs + when_off, 32 * (size_t)std::min(rows, H));
-        memcpy(ord->exact_until, hs + until_off, 4 * (size_t)std::min(rows, H));
+        memcpy(ord->when, hs + when_off, kWhenRow * staged);
+        memcpy(ord->exact_until, hs + until_off, kUntilRow * staged);
     }
     if (rows > H) {   // more rounds than staged: the overflow columns, straight into out
         const uint32_t e = rows - H;
-        struct Piece {
-            void* dst;
-            const void* src;
-            size_t sz;
-        } pieces[] = {
-            {out->height + H, oc.h, 8 * (size_t)e},           {out->round + H, oc.r, 8 * (size_t)e},
-            {out->rep + H, oc.rep, 4 * (size_t)e},            {out->propose + H, oc.propose, 4 * (size_t)e},
-            {out->prevotes + H, oc.prevotes, 4 * (size_t)e},  {out->precommits + H, oc.precommits, 4 * (size_t)e},
-            {out->trace + H, oc.trace, 4 * (size_t)e},        {out->pv_value + H, oc.pv_value, 4 * (size_t)e},
-            {out->pc_value + H, oc.pc_value, 4 * (size_t)e},  {out->pv_nil + H, oc.pv_nil, 4 * (size_t)e},
-            {out->pv_validround + H, oc.pv_validround, 4 * (size_t)e},
-            {out->flags + H, oc.flags, (size_t)e},            {out->bits + H, oc.bits, (size_t)e},
-        };
-        for (const Piece& p : pieces) TCHK(hipMemcpyAsync(p.dst, p.src, p.sz, hipMemcpyDeviceToHost, s), "decide overflow");
+        const auto down = copy_down(s);
+        if ((rc = cols_copy(ctx, kDecideCols, ovf, m, e, H, out, down))) return rc;
         if (ord) {
-            TCHK(hipMemcpyAsync(ord->when + 8 * (size_t)H, ovf + ovw_off, 32 * (size_t)e, hipMemcpyDeviceToHost, s),
-                 "decide overflow when");
-            TCHK(hipMemcpyAsync(ord->exact_until + H, ovf + ovu_off, 4 * (size_t)e, hipMemcpyDeviceToHost, s),
-                 "decide overflow until");
+            TCHK(down(ord->when + 8 * (size_t)H, ovf + ovw_off, kWhenRow * e), "decide overflow when");
+            TCHK(down(ord->exact_until + H, ovf + ovu_off, kUntilRow * e), "decide overflow until");
         }
         TCHK(hipStreamSynchronize(s), "decide overflow sync");
     }

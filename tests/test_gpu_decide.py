@@ -333,6 +333,91 @@ def test_more_rounds_than_staged(gpu, oracle):
         v.close()
 
 
+# ---- 6b. one plan for tally and decide, across table capacities ---------------
+def _capacity_sequence(hd, O):
+    """Tally, decide and decide_ordered share one table plan on a context's
+    buffers.  300 messages take tables of 1,024 slots and 3,000 take 8,192, so
+    every step below meets tables the previous step left at the other capacity
+    (or, from step 3 on, an allocation that is larger than the step needs).
+    Each result equals the oracle / restatement / replay and the same call on a
+    fresh context."""
+    import when_cases as WC
+    rng = random.Random(11)
+    sigs = [O.sha256(b"p" + bytes([k])) for k in range(30)]
+    vals = [O.canonical_value(1, k) for k in range(2)] + [O.NIL_VALUE]
+    f = 3
+    small = _mix(O, rng, 300, [1, 2], list(range(4)), sigs, vals, 1 / 8)
+    big = _mix(O, rng, 3000, [1, 2, 3, 4], list(range(6)), sigs, vals, 1 / 8)
+
+    def tally(v, mix):
+        ob, verdicts, _ = mix
+        tal = v.tally(to_np(ob), np.array(verdicts, np.uint8))
+        return (tal.count, tal.distinct, tal.distinct_any, tal.dup.tolist())
+
+    def tally_want(mix):
+        ot = O.tally(mix[0], mix[1])
+        return lambda got: got == (ot.count, ot.distinct, ot.distinct_any, ot.dup)
+
+    def decide(v, mix):
+        ob, verdicts, value_ok = mix
+        res = _decide(v, ob, verdicts, f, None, value_ok)
+        return tuple(getattr(res, k).tobytes() for k in PC.ROW_FIELDS + ("pclass", "dup")), res
+
+    def decide_want(mix):
+        want = PC.restate(mix[0], mix[1], f, None, mix[2])
+        return lambda got: PC.same_as(got[1], want) is None
+
+    def ordered(v, mix):
+        ob, verdicts, value_ok = mix
+        res = v.decide_ordered(to_np(ob), np.array(verdicts, np.uint8), f, value_ok=np.array(value_ok, np.uint8))
+        rows = tuple(getattr(res, k).tobytes() for k in PC.ROW_FIELDS + ("pclass", "dup"))
+        return rows + (res.when.tobytes(), res.exact_until.tobytes()), res
+
+    def ordered_want(mix):
+        want, logs = PC.restate(mix[0], mix[1], f, None, mix[2]), WC.replay(mix[0], mix[1], f, None, mix[2])
+        return lambda got: PC.same_as(got[1], want) is None and WC.same_when(got[1], logs) is None
+
+    steps = [(tally, tally_want, small), (decide, decide_want, big), (tally, tally_want, small),
+             (ordered, ordered_want, big), (decide, decide_want, small), (tally, tally_want, big)]
+    shared = hd.Verifier(0)
+    try:
+        shared.set_signatories(_rows(sigs[:15]))
+        for k, (call, want, mix) in enumerate(steps):
+            got = call(shared, mix)
+            assert want(mix)(got), k
+            fresh = hd.Verifier(0)
+            try:
+                fresh.set_signatories(_rows(sigs[:15]))
+                alone = call(fresh, mix)
+            finally:
+                fresh.close()
+            same = got == alone if call is tally else got[0] == alone[0]
+            assert same, k
+    finally:
+        shared.close()
+
+
+def test_plan_shared_across_capacities(gpu, oracle):
+    _capacity_sequence(gpu, oracle)
+
+
+def test_plan_shared_across_capacities_checked():
+    """The same sequence with HD_TALLY_CHECK=1: every tally call then also
+    asserts the table invariants and that the emit left the tables clean.  The
+    variable is set for a fresh child process, so that nothing else in this
+    process runs under it."""
+    import os
+    import subprocess
+    import sys
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    code = ("import sys; sys.path[:0] = %r; import hd_pyoracle as O, hyperdrive_amd as hd, test_gpu_decide as T; "
+            "T._capacity_sequence(hd, O); print('sequence ok')" % [here, root, os.path.join(root, "oracle")])
+    r = subprocess.run([sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code],
+                       env=dict(os.environ, HD_TALLY_CHECK="1"), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "sequence ok" in r.stdout, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+
+
 # ---- 7. the device entry on generated data ------------------------------------
 @pytest.mark.parametrize("adv", [0, 30])
 def test_device_entry_on_generated_rounds(verifier, oracle, adv):
