@@ -110,6 +110,12 @@ class HdDecideOrder(ctypes.Structure):
     _fields_ = [("cap", ctypes.c_uint32), ("when", ctypes.c_void_p), ("exact_until", ctypes.c_void_p)]
 
 
+class HdCatchOut(ctypes.Structure):
+    """include/hd_verify.h hd_catch_out (hd_decide_catch*, hd_log_insert_catch*)."""
+    _fields_ = [("cap", ctypes.c_uint32), ("n", ctypes.c_uint32), ("index", ctypes.c_void_p),
+                ("against", ctypes.c_void_p), ("kind", ctypes.c_void_p)]
+
+
 class HdLogInfo(ctypes.Structure):
     """include/hd_log.h hd_log_info (hd_log_insert / hd_log_insert_device_bitmap)."""
     _fields_ = [("base", ctypes.c_uint32), ("kept", ctypes.c_uint32), ("relogged", ctypes.c_uint32),
@@ -191,6 +197,13 @@ SIGNATURES = {
     "hd_decide_ordered_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
                                                        ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
                                                        ctypes.POINTER(HdDecideOrder), ctypes.c_void_p]),
+    "hd_decide_catch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                       ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
+                                       ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdCatchOut)]),
+    "hd_decide_catch_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                                     ctypes.POINTER(HdDecideIn), ctypes.POINTER(HdDecideOut),
+                                                     ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdCatchOut),
+                                                     ctypes.c_void_p]),
     # include/hd_log.h
     "hd_log_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_log_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -205,6 +218,14 @@ SIGNATURES = {
                                                    ctypes.c_void_p, ctypes.POINTER(HdDecideOut),
                                                    ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
                                                    ctypes.c_void_p]),
+    "hd_log_insert_catch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.POINTER(HdDecideOut),
+                                           ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
+                                           ctypes.POINTER(HdCatchOut)]),
+    "hd_log_insert_catch_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.POINTER(HdDecideOut),
+                                                         ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
+                                                         ctypes.POINTER(HdCatchOut), ctypes.c_void_p]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

@@ -114,9 +114,13 @@ struct DecideExt {
 };
 // Whole batch only; device batch, verdict bytes or valid bitmap, in.sched32 and
 // in.value_ok; host outputs; synchronises s.  ord: the ordered form's output
-// or NULL; ext: NULL for hd_decide* themselves.
+// or NULL; ext: NULL for hd_decide* themselves; caught: the catch list (arrays
+// checked by the caller) or NULL, with which the launches are the same as before
+// the list existed.  HD_ECAP when either the rows or the records do not fit,
+// with out->n and caught->n both set.
 int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap, DecideIn in,
-                  hd_decide_out* out, hipStream_t s, hd_decide_order* ord, const DecideExt* ext);
+                  hd_decide_out* out, hipStream_t s, hd_decide_order* ord, const DecideExt* ext,
+                  hd_catch_out* caught);
 
 // known-key fast path (hd_fastverify.hip)
 int hd_fb_init(hd_ctx* ctx);                    // tables of G (slot 0); at context creation

@@ -12,7 +12,9 @@
 //                  is VALID, a new message only when its verdict / bitmap bit
 //                  says so and its height is the log's -- and value_ok byte
 //   hd_decide_run  the ordered decide passes over the L + n items
-//                  (hd_tally.hip), with dup / pclass left on the device
+//                  (hd_tally.hip), with dup / pclass left on the device; the
+//                  catch list, when asked for, is in these joined coordinates
+//                  as it leaves the decide
 //   k_log_count    per block of 256 joined positions: how many retained
 //                  entries came out logged again and how many new messages are
 //                  kept (dup == 0 or pclass == 0); ballot / popcount per
@@ -30,7 +32,8 @@
 //                  bytes next to it, so the insert downloads one small block.
 //
 // The host reads [kept, relogged | logpos | dup | pclass] from a pinned stage
-// after the decide's one synchronisation; the log's length moves only after
+// after the decide's one synchronisation (a class the caller passes NULL for
+// is left out of the block: it is neither gathered nor downloaded); the log's length moves only after
 // every check has passed, so any error leaves the log as it was.
 #include <hip/hip_runtime.h>
 
@@ -75,7 +78,7 @@ struct hd_log {
     LogCols tmp{};                // the kept rows of one insert: cap_new rows
     size_t cap_new = 0;
     DevBuf blk;                   // two totals per block of 256 joined positions
-    DevBuf res;                   // [kept, relogged .. 64 B | logpos 4n | dup n | pclass n]
+    DevBuf res;                   // [kept, relogged .. 64 B | logpos 4n | dup n | pclass n], the classes when taken
     DevBuf in_vok;                // the host form's uploaded value_ok
     char* host = nullptr;         // pinned image of res
     size_t host_cap = 0;
@@ -175,8 +178,8 @@ __global__ __launch_bounds__(256) void k_log_keep(uint32_t total, uint32_t L, co
     for (uint32_t k = 0; k < w; k++) off += wn[k];
     const uint32_t j = off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
     const uint32_t i = q - L;
-    o_dup[i] = du;
-    o_pclass[i] = pc;
+    if (o_dup) o_dup[i] = du;         // a class the caller does not take is not gathered
+    if (o_pclass) o_pclass[i] = pc;
     logpos[i] = keep ? L + j : HD_WHEN_NEVER;
     if (keep) {   // j < the batch's size: tmp has a row for every new message
         copy_row(tmp, j, lg.type, lg.height, lg.round, lg.vround, lg.value32, lg.from32, q);
@@ -243,7 +246,7 @@ static size_t log_pad(size_t n) { return (n + 63) & ~(size_t)63; }
 struct KeepArgs {
     hd_log* lg;
     uint32_t n, total, nb;
-    size_t res_bytes;
+    size_t dup_off, pc_off, res_bytes;   // dup_off / pc_off: 0 when the caller does not take the class
 };
 
 // hd_decide_run's hook: dup / pclass are complete on the stream
@@ -254,10 +257,11 @@ static int log_queue_keep(void* arg, hipStream_t s) {
     char* res = (char*)lg->res.p;
     const uint8_t *dup = (const uint8_t*)lg->dup.p, *pclass = (const uint8_t*)lg->pclass.p;
     uint32_t* blk = (uint32_t*)lg->blk.p;
-    const size_t lp_off = 64, dup_off = lp_off + log_pad(4 * (size_t)a->n), pc_off = dup_off + log_pad(a->n);
+    const size_t lp_off = 64;
     k_log_count<<<a->nb, 256, 0, s>>>(a->total, lg->L, dup, pclass, blk);
     k_log_keep<<<a->nb, 256, 0, s>>>(a->total, lg->L, dup, pclass, blk, lg->lg, lg->tmp, (uint32_t*)res,
-                                     (uint32_t*)(res + lp_off), (uint8_t*)(res + dup_off), (uint8_t*)(res + pc_off));
+                                     (uint32_t*)(res + lp_off), a->dup_off ? (uint8_t*)(res + a->dup_off) : nullptr,
+                                     a->pc_off ? (uint8_t*)(res + a->pc_off) : nullptr);
     LCHK(hipGetLastError(), "log keep kernels");
     LCHK(hipMemcpyAsync(lg->host, res, a->res_bytes, hipMemcpyDeviceToHost, s), "log download");
     return HD_OK;
@@ -272,7 +276,7 @@ static bool log_out_ok(const hd_decide_out* o, const hd_decide_order* w) {
 // db, d_verdict / d_bitmap (one of them) and d_vok are device pointers
 static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, const uint32_t* d_bitmap,
                       const uint8_t* d_vok, hd_decide_out* out, hd_decide_order* order, hd_log_info* info,
-                      hipStream_t s) {
+                      hd_catch_out* caught, hipStream_t s) {
     hd_ctx* ctx = lg->ctx;
     const uint32_t n = db->n, L = lg->L, total = L + n;
     if (total == 0) return HD_OK;
@@ -283,7 +287,11 @@ static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, 
     if (!rc) rc = buf_grow(ctx, lg->dup, total);
     if (!rc) rc = buf_grow(ctx, lg->pclass, total);
     if (!rc) rc = buf_grow(ctx, lg->blk, 8 * (size_t)nb);
-    const size_t res_bytes = 64 + log_pad(4 * (size_t)n) + 2 * log_pad(n);
+    // [header | logpos | dup, when out->dup | pclass, when out->pclass]: a class the caller passes NULL for
+    // stays in lg->dup / lg->pclass on the device and is neither gathered nor downloaded
+    const size_t cls_off = 64 + log_pad(4 * (size_t)n);
+    const size_t dup_off = out->dup ? cls_off : 0, pc_off = out->pclass ? cls_off + (out->dup ? log_pad(n) : 0) : 0;
+    const size_t res_bytes = cls_off + (out->dup ? log_pad(n) : 0) + (out->pclass ? log_pad(n) : 0);
     if (!rc) rc = buf_grow(ctx, lg->res, res_bytes);
     if (rc) return rc;
     if (lg->host_cap < res_bytes) {
@@ -306,13 +314,19 @@ static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, 
     jb.value32 = lg->lg.value32;
     jb.from32 = lg->lg.from32;
     jb.sig65 = nullptr;
-    KeepArgs ka{lg, n, total, nb, res_bytes};
+    KeepArgs ka{lg, n, total, nb, dup_off, pc_off, res_bytes};
     const DecideExt ext{(uint8_t*)lg->dup.p, (uint8_t*)lg->pclass.p, log_queue_keep, &ka};
     rc = hd_decide_run(ctx, &jb, (const uint8_t*)lg->vd.p, nullptr,
                        DecideIn{lg->f, lg->n_sched, lg->n_sched ? lg->d_sched : nullptr, lg->lg.vok}, out, s, order,
-                       &ext);
+                       &ext, caught);
     (void)hd_ctx_note_stream(ctx, s);
     if (rc) return rc;
+    // the items are the joined coordinates, so the records are final; they are in ascending index and a
+    // retained entry, the only message of its key, is never an offender
+    if (caught && caught->n && caught->index[0] < L) {
+        ctx->last_error = "hd_log: the replay reported a retained entry as an offender";
+        return HD_EDEVICE;
+    }
     const uint32_t* hdr = reinterpret_cast<const uint32_t*>(lg->host);
     const uint32_t kept = hdr[0], relogged = hdr[1];
     info->kept = kept;
@@ -322,7 +336,7 @@ static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, 
         return HD_EDEVICE;
     }
     if (lg->max_entries && (uint64_t)L + kept > lg->max_entries) return HD_ECAP;
-    const size_t lp_off = 64, dup_off = lp_off + log_pad(4 * (size_t)n), pc_off = dup_off + log_pad(n);
+    const size_t lp_off = 64;
     if (info->logpos) memcpy(info->logpos, lg->host + lp_off, 4 * (size_t)n);
     if (out->dup) memcpy(out->dup, lg->host + dup_off, n);
     if (out->pclass) memcpy(out->pclass, lg->host + pc_off, n);
@@ -337,10 +351,57 @@ static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, 
 }
 
 static bool log_args_ok(const hd_log* lg, const hd_batch* b, const hd_decide_out* out, const hd_decide_order* order,
-                        hd_log_info* info) {
+                        hd_log_info* info, const hd_catch_out* caught) {
     if (!lg || !lg->ctx || !b || !info || !log_out_ok(out, order)) return false;
+    if (caught && caught->cap && (!caught->index || !caught->against || !caught->kind)) return false;
     if (b->n && (!b->type || !b->height || !b->round || !b->value32 || !b->from32)) return false;
     return (uint64_t)lg->L + b->n < (1ull << 30);
+}
+
+// hd_log_insert and hd_log_insert_catch (caught non-NULL, checked by the caller)
+static int insert_host(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
+                       hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught) {
+    if (!log_args_ok(lg, batch, out, order, info, caught) || (batch->n && !verdict)) return HD_EINVAL;
+    hd_ctx* ctx = lg->ctx;
+    out->n = 0;
+    if (caught) caught->n = 0;
+    info->base = lg->L;
+    info->kept = info->relogged = 0;
+    const uint32_t n = batch->n;
+    (void)hipSetDevice(ctx->device);
+    hd_batch db;
+    memset(&db, 0, sizeof db);
+    const uint8_t *d_v = nullptr, *d_vok = nullptr;
+    if (n) {
+        hd_batch hb = *batch;
+        hb.sig65 = nullptr;   // not kept: Equal ignores it
+        int rc = hd_upload_batch(ctx, &hb, &db);
+        if (!rc) rc = hd_dev_grow(ctx, &ctx->bufs[BUF_VERDICT].p, &ctx->bufs[BUF_VERDICT].cap, n);
+        if (!rc && value_ok) rc = buf_grow(ctx, lg->in_vok, n);
+        if (rc) return rc;
+        LCHK(hipMemcpyAsync(ctx->bufs[BUF_VERDICT].p, verdict, n, hipMemcpyHostToDevice, ctx->stream),
+             "verdict upload");
+        d_v = (const uint8_t*)ctx->bufs[BUF_VERDICT].p;
+        if (value_ok) {
+            LCHK(hipMemcpyAsync(lg->in_vok.p, value_ok, n, hipMemcpyHostToDevice, ctx->stream), "value_ok upload");
+            d_vok = (const uint8_t*)lg->in_vok.p;
+        }
+    }
+    return log_insert(lg, &db, d_v, nullptr, d_vok, out, order, info, caught, ctx->stream);
+}
+
+static int insert_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap, const uint8_t* d_value_ok,
+                         hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught,
+                         void* stream) {
+    if (!log_args_ok(lg, dbatch, out, order, info, caught) || (dbatch->n && !d_valid_bitmap)) return HD_EINVAL;
+    hd_ctx* ctx = lg->ctx;
+    out->n = 0;
+    if (caught) caught->n = 0;
+    info->base = lg->L;
+    info->kept = info->relogged = 0;
+    (void)hipSetDevice(ctx->device);
+    return log_insert(lg, dbatch, nullptr, dbatch->n ? d_valid_bitmap : nullptr, d_value_ok, out, order, info, caught,
+                      stream ? (hipStream_t)stream : ctx->stream);
 }
 
 extern "C" {
@@ -399,45 +460,26 @@ int hd_log_len(const hd_log* lg, int64_t* height, uint32_t* entries) {
 
 int hd_log_insert(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
                   hd_decide_out* out, hd_decide_order* order, hd_log_info* info) {
-    if (!log_args_ok(lg, batch, out, order, info) || (batch->n && !verdict)) return HD_EINVAL;
-    hd_ctx* ctx = lg->ctx;
-    out->n = 0;
-    info->base = lg->L;
-    info->kept = info->relogged = 0;
-    const uint32_t n = batch->n;
-    (void)hipSetDevice(ctx->device);
-    hd_batch db;
-    memset(&db, 0, sizeof db);
-    const uint8_t *d_v = nullptr, *d_vok = nullptr;
-    if (n) {
-        hd_batch hb = *batch;
-        hb.sig65 = nullptr;   // not kept: Equal ignores it
-        int rc = hd_upload_batch(ctx, &hb, &db);
-        if (!rc) rc = hd_dev_grow(ctx, &ctx->bufs[BUF_VERDICT].p, &ctx->bufs[BUF_VERDICT].cap, n);
-        if (!rc && value_ok) rc = buf_grow(ctx, lg->in_vok, n);
-        if (rc) return rc;
-        LCHK(hipMemcpyAsync(ctx->bufs[BUF_VERDICT].p, verdict, n, hipMemcpyHostToDevice, ctx->stream),
-             "verdict upload");
-        d_v = (const uint8_t*)ctx->bufs[BUF_VERDICT].p;
-        if (value_ok) {
-            LCHK(hipMemcpyAsync(lg->in_vok.p, value_ok, n, hipMemcpyHostToDevice, ctx->stream), "value_ok upload");
-            d_vok = (const uint8_t*)lg->in_vok.p;
-        }
-    }
-    return log_insert(lg, &db, d_v, nullptr, d_vok, out, order, info, ctx->stream);
+    return insert_host(lg, batch, verdict, value_ok, out, order, info, nullptr);
 }
 
 int hd_log_insert_device_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
                                 const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
                                 hd_log_info* info, void* stream) {
-    if (!log_args_ok(lg, dbatch, out, order, info) || (dbatch->n && !d_valid_bitmap)) return HD_EINVAL;
-    hd_ctx* ctx = lg->ctx;
-    out->n = 0;
-    info->base = lg->L;
-    info->kept = info->relogged = 0;
-    (void)hipSetDevice(ctx->device);
-    return log_insert(lg, dbatch, nullptr, dbatch->n ? d_valid_bitmap : nullptr, d_value_ok, out, order, info,
-                      stream ? (hipStream_t)stream : ctx->stream);
+    return insert_bitmap(lg, dbatch, d_valid_bitmap, d_value_ok, out, order, info, nullptr, stream);
+}
+
+int hd_log_insert_catch(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
+                        hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught) {
+    if (!caught) return HD_EINVAL;
+    return insert_host(lg, batch, verdict, value_ok, out, order, info, caught);
+}
+
+int hd_log_insert_catch_device_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                      const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
+                                      hd_log_info* info, hd_catch_out* caught, void* stream) {
+    if (!caught) return HD_EINVAL;
+    return insert_bitmap(lg, dbatch, d_valid_bitmap, d_value_ok, out, order, info, caught, stream);
 }
 
 }  // extern "C"

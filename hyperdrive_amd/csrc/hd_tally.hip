@@ -35,7 +35,8 @@
 // and turns each round's counts into one row with the eight predicate bits.
 // hd_decide_ordered adds a sort of the logged votes by (round, batch index)
 // and a per-row walk that finds the message at which each predicate first
-// holds in batch order.
+// holds in batch order.  hd_decide_catch adds the list of offences, each with
+// the logged message it contradicts (two passes before the tables are cleaned).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -57,7 +58,7 @@ using namespace hd;
 static const uint32_t kEmpty = 0xFFFFFFFFu;
 
 struct TallyWork {
-    DevBuf b[24];
+    DevBuf b[24];   // one per TSlot (static_assert below the enum)
     void* host = nullptr;   // pinned download stage (hipHostMalloc)
     size_t host_cap = 0;
     uint32_t* scalar = nullptr;   // pinned word (a partition's candidate count)
@@ -72,6 +73,7 @@ struct TallyWork {
         uint32_t k = 0;
     } tab, ptab;   // ptab: hd_decide's propose claim table (cleaned by k_decide_clean)
     std::atomic<uint32_t> guess_dec{1024};   // hd_decide: the staged row capacity
+    std::atomic<uint32_t> guess_catch{1024}; // hd_decide_catch: the staged record capacity
 };
 // T_G: the hash tables and call counters; T_C: the dense log cells; T_D /
 // T_SORTK / T_TMP: a partition's candidate compaction; T_GSLOT / T_DSLOT /
@@ -83,9 +85,11 @@ struct TallyWork {
 // T_DSTAGE / T_DOVF its output stage and overflow rows, T_SCHED / T_VOK the
 // host form's uploaded schedule and value_ok bytes; hd_decide_ordered: T_WKEY /
 // T_WVAL the per-item sort keys and batch indices (unsorted | sorted), T_WTMP
-// the radix sort's temporary storage
+// the radix sort's temporary storage; hd_decide_catch: T_CATCH the overflow
+// records and, when the caller takes no classes, the classes' scratch
 enum TSlot { T_G, T_D, T_C, T_GSLOT, T_DSLOT, T_NSEL, T_SEL, T_SORTK, T_TMP, T_DUP, T_ROUTE, T_CHECK,
-             T_CSLOT, T_BITS, T_P, T_PSLOT, T_DSTAGE, T_DOVF, T_SCHED, T_VOK, T_WKEY, T_WVAL, T_WTMP };
+             T_CSLOT, T_BITS, T_P, T_PSLOT, T_DSTAGE, T_DOVF, T_SCHED, T_VOK, T_WKEY, T_WVAL, T_WTMP, T_CATCH, T_COUNT };
+static_assert(T_COUNT == sizeof(TallyWork::b) / sizeof(DevBuf), "a buffer for every TSlot");
 
 // table layouts (structure of arrays inside one allocation, capacity cap)
 struct GTab {   // (h, r)
@@ -2134,6 +2138,130 @@ __global__ __launch_bounds__(256) void k_decide_when(DevBatch b, uint32_t m, Dec
     }
 }
 
+// ------------------------------------------------------------ decide, catch
+// hd_decide_catch: the offences of a batch, each with the logged message it
+// contradicts -- the arguments of Catcher.CatchDoublePropose / CatchDoublePrevote
+// / CatchDoublePrecommit / CatchOutOfTurnPropose (process.go:771-793, 838-841,
+// 875-878).  A message has a record exactly when dup == 2 or pclass is 2 or 4,
+// and the logged message is the winner the classifying kernel compared it
+// with: the log cell its `ref` names (a dense cell, or a slot of D) for a vote,
+// P[pslot] for a propose.  The passes run where the ordered passes run,
+// between k_decide_emit and k_decide_clean, and read the winner again from
+// the populated tables; k_tally_values and k_decide_log stay as they are (the
+// tally runs the first beside every verification).  Records are in batch
+// order by the firsts / emit idiom above -- ballot words, popcount prefixes,
+// block totals summed by every emit block: no sort, no atomics.
+//
+//   k_catch_flags   "has a record" per item as whole bitmap words, their
+//                   prefix within the block and the block's total.  The words
+//                   go where k_tally_firsts put Bc / pre_c and the C half of
+//                   the block totals: nothing reads those after the firsts
+//                   pass of a decide (k_decide_clean reads Bg only)
+//   k_catch_emit    each flagged item writes (index, against, kind) at its
+//                   position, into the stage below the staged capacity and
+//                   into the overflow columns past it; the last block writes
+//                   the record count into word 1 of the stage header
+struct CatchCols {
+    uint32_t *index, *against;
+    uint8_t* kind;
+};
+constexpr Col kCatchCols[] = {
+    HD_COL(CatchCols, index, hd_catch_out, index), HD_COL(CatchCols, against, hd_catch_out, against),
+    HD_COL(CatchCols, kind, hd_catch_out, kind),
+};
+constexpr size_t kCatchRow = row_bytes(kCatchCols);
+static_assert(kCatchRow == 2 * 4 + 1, "catch record bytes");
+static_assert(sizeof(kCatchCols) / sizeof(Col) == sizeof(CatchCols) / sizeof(void*), "every CatchCols pointer is a column");
+
+HD_HOSTONLY CatchCols catch_cols(char* base, uint32_t cap) {
+    CatchCols x;
+    cols_layout(kCatchCols, base, cap, &x);
+    return x;
+}
+
+__device__ __forceinline__ bool has_record(const uint8_t* dup, const uint8_t* pclass, uint32_t q) {
+    const uint8_t pc = pclass[q];
+    return dup[q] == 2 || pc == 2 || pc == 4;
+}
+
+template <uint32_t IPB>
+__global__ __launch_bounds__(256) void k_catch_flags(uint32_t m, const uint8_t* __restrict__ dup,
+                                                     const uint8_t* __restrict__ pclass, uint32_t* __restrict__ Bx,
+                                                     uint32_t* __restrict__ pre_x, uint32_t* __restrict__ blk_x) {
+    constexpr uint32_t W = IPB / 32;   // words per block (<= 64: one wavefront scans them)
+    __shared__ uint32_t wx[W];
+    const uint32_t lo = blockIdx.x * IPB;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (uint32_t k = 0; k < IPB / 256; k++) {
+        const uint32_t q = lo + k * 256 + threadIdx.x;
+        const unsigned long long bx = __ballot(q < m && has_record(dup, pclass, q));
+        if (lane == 0) {
+            const uint32_t w = k * 8 + wave * 2;
+            wx[w] = (uint32_t)bx;
+            wx[w + 1] = (uint32_t)(bx >> 32);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < W) {   // one lane per word (wavefront 0)
+        const uint32_t t = threadIdx.x, xw = wx[t];
+        uint32_t ix = (uint32_t)__popc(xw);
+        for (int d = 1; d < 64; d <<= 1) {   // inclusive scan across the wavefront
+            const uint32_t yx = (uint32_t)__shfl_up((int)ix, d, 64);
+            if ((int)t >= d) ix += yx;
+        }
+        const size_t wi = (size_t)blockIdx.x * W + t;
+        Bx[wi] = xw;
+        pre_x[wi] = ix - (uint32_t)__popc(xw);
+        if (t == W - 1) blk_x[blockIdx.x] = ix;
+    }
+}
+
+template <uint32_t IPB>
+__global__ __launch_bounds__(256) void k_catch_emit(DevBatch b, uint32_t m, const uint8_t* __restrict__ dup,
+                                                    const uint8_t* __restrict__ pclass,
+                                                    const uint32_t* __restrict__ ref,
+                                                    const uint32_t* __restrict__ pslot,
+                                                    const uint32_t* __restrict__ Dd, const uint32_t* __restrict__ D,
+                                                    const uint32_t* __restrict__ P, const uint32_t* __restrict__ Bx,
+                                                    const uint32_t* __restrict__ pre_x,
+                                                    const uint32_t* __restrict__ blk_x, CatchCols st, uint32_t H,
+                                                    CatchCols ov, uint32_t* stage_hdr) {
+    const uint32_t nb = gridDim.x;
+    __shared__ uint32_t part[4];
+    uint32_t sx = 0;
+    for (uint32_t k = threadIdx.x; k < blockIdx.x; k += 256) sx += blk_x[k];
+    for (int d = 32; d > 0; d >>= 1) sx += (uint32_t)__shfl_xor((int)sx, d, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sx;
+    __syncthreads();
+    const uint32_t ox = part[0] + part[1] + part[2] + part[3];
+    if (threadIdx.x == 0 && blockIdx.x == nb - 1) stage_hdr[1] = ox + blk_x[nb - 1];   // records
+    const uint32_t lo = blockIdx.x * IPB;
+    for (uint32_t k = 0; k < IPB / 256; k++) {
+        const uint32_t q = lo + k * 256 + threadIdx.x;
+        if (q >= m) break;
+        const uint32_t w = q >> 5, xw = Bx[w];
+        if (!((xw >> (q & 31)) & 1u)) continue;
+        const uint32_t pos = ox + pre_x[w] + (uint32_t)__popc(xw & ((1u << (q & 31)) - 1u));
+        uint32_t against = HD_WHEN_NEVER;
+        uint8_t kind = HD_CATCH_OUT_OF_TURN;
+        if (dup[q] == 2) {   // a candidate vote: ref names its log cell, which holds the logged vote
+            const uint32_t rf = ref[q];
+            against = (rf & HD_REF_HASHED) ? D[rf & ~HD_REF_HASHED] : Dd[rf];
+            kind = b.type[q] == T_PREVOTE ? HD_CATCH_DOUBLE_PREVOTE : HD_CATCH_DOUBLE_PRECOMMIT;
+        } else if (pclass[q] == 2) {   // an eligible propose: its round's slot of P holds the logged propose
+            against = P[pslot[q]];
+            kind = HD_CATCH_DOUBLE_PROPOSE;
+        }
+        const CatchCols& x = pos < H ? st : ov;
+        const uint32_t j = pos < H ? pos : pos - H;
+        x.index[j] = q;
+        x.against[j] = against;
+        x.kind[j] = kind;
+    }
+}
+
+static bool catch_out_ok(const hd_catch_out* c) { return c && (c->cap == 0 || (c->index && c->against && c->kind)); }
+
 static bool decide_out_ok(const hd_decide_out* o) {
     return o && o->height && o->round && o->rep && o->propose && o->prevotes && o->precommits && o->trace &&
            o->pv_value && o->pc_value && o->pv_nil && o->pv_validround && o->flags && o->bits;
@@ -2151,9 +2279,15 @@ static bool decide_order_ok(const hd_decide_out* o, const hd_decide_order* w, ui
 // of copies.  With `ord` (hd_decide_ordered) the stage continues with
 // [when (8 words per row) | exact_until] at capacity H, and the overflow
 // buffer likewise after its rows.  With `ext` (hd_log.hip) the classes go to
-// the caller's device arrays instead of the stage (hd_internal.h).
+// the caller's device arrays instead of the stage (hd_internal.h).  With
+// `caught` (hd_decide_catch) the stage ends with the catch records at a staged
+// capacity of their own, their count in word 1 of the header; records past
+// that capacity come from T_CATCH with the overflow rows.  The catch passes
+// read both classes, so a class the caller does not take stays in T_CATCH and
+// is not downloaded.
 int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, const uint32_t* d_bitmap, DecideIn in,
-                  hd_decide_out* out, hipStream_t s, hd_decide_order* ord, const DecideExt* ext) {
+                  hd_decide_out* out, hipStream_t s, hd_decide_order* ord, const DecideExt* ext,
+                  hd_catch_out* caught) {
     const uint32_t n = hb->n, m = n;
     if (!ctx->tally) ctx->tally = new TallyWork();
     TallyWork* tw = ctx->tally;
@@ -2163,11 +2297,22 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
     const bool st_dup = !ext && out->dup, st_pclass = !ext && out->pclass;   // staged and downloaded
     const size_t dup_off = 64, pc_off = dup_off + (st_dup ? pad64(n) : 0), rows_off = pc_off + (st_pclass ? pad64(n) : 0);
     const size_t when_off = rows_off + pad64(kDecideRow * H), until_off = when_off + kWhenRow * H;
-    const size_t total = ord ? until_off + kUntilRow * H + 64 : rows_off + kDecideRow * H + 64;
+    const size_t total0 = ord ? until_off + kUntilRow * H + 64 : rows_off + kDecideRow * H + 64;
+    const uint32_t Hc = caught ? tw->guess_catch.load() : 0u;
+    const size_t catch_off = pad64(total0), total = caught ? catch_off + kCatchRow * Hc + 64 : total0;
     char* st = (char*)tbuf(ctx, T_DSTAGE, total, &rc);
     if (rc) return rc;
     uint8_t* d_dup = ext ? ext->d_dup : st_dup ? (uint8_t*)(st + dup_off) : nullptr;
     uint8_t* d_pclass = ext ? ext->d_pclass : st_pclass ? (uint8_t*)(st + pc_off) : nullptr;
+    // the catch list's overflow records (capacity m), then the classes nobody downloads
+    char* covf = nullptr;
+    if (caught) {
+        const size_t cls_off = pad64(kCatchRow * m + 64);
+        covf = (char*)tbuf(ctx, T_CATCH, cls_off + 2 * pad64(n), &rc);
+        if (rc) return rc;
+        if (!d_dup) d_dup = (uint8_t*)(covf + cls_off);
+        if (!d_pclass) d_pclass = (uint8_t*)(covf + cls_off + pad64(n));
+    }
     // the overflow rows (capacity m), the ordered form's after them
     const size_t ovw_off = pad64(kDecideRow * m + 64), ovu_off = ovw_off + kWhenRow * m;
     char* ovf = (char*)tbuf(ctx, T_DOVF, ord ? ovu_off + kUntilRow * m + 64 : kDecideRow * m + 64, &rc);
@@ -2220,6 +2365,15 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
                                             (uint32_t*)(st + when_off), (uint32_t*)(st + until_off),
                                             (uint32_t*)(ovf + ovw_off), (uint32_t*)(ovf + ovu_off));
     }
+    if (caught) {   // likewise; Bc, pre_c and the C totals are free after the firsts pass
+        const CatchCols cs = catch_cols(st + catch_off, Hc), co = catch_cols(covf, m);
+        with_ipb(p.ipb, [&](auto ipb) {
+            constexpr uint32_t IPB = decltype(ipb)::value;
+            k_catch_flags<IPB><<<p.nbo, 256, 0, s>>>(m, d_dup, d_pclass, p.Bc, p.pre_c, p.blk + p.nbo);
+            k_catch_emit<IPB><<<p.nbo, 256, 0, s>>>(b, m, d_dup, d_pclass, p.ref, p.pslot, p.Dd, p.d, p.P, p.Bc,
+                                                    p.pre_c, p.blk + p.nbo, cs, Hc, co, (uint32_t*)st);
+        });
+    }
     k_decide_clean<<<p.grid, 256, 0, s>>>(m, p.gslot, p.cslot, p.ref, p.pslot, p.G, p.C, p.d, p.P, p.Bg, p.ctr);
     TCHK(hipGetLastError(), "decide order kernels");
     tally_plan_done(ctx, p);
@@ -2232,7 +2386,12 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
     const uint32_t rows = reinterpret_cast<const uint32_t*>(hs)[0];
     out->n = rows;
     tw->guess_dec = std::max<uint32_t>(1024u, rows + rows / 4);
-    if (rows > out->cap) return HD_ECAP;
+    const uint32_t recs = caught ? reinterpret_cast<const uint32_t*>(hs)[1] : 0u;
+    if (caught) {
+        caught->n = recs;
+        tw->guess_catch = std::max<uint32_t>(1024u, recs + recs / 4);
+    }
+    if (rows > out->cap || (caught && recs > caught->cap)) return HD_ECAP;
     if (st_dup) memcpy(out->dup, hs + dup_off, n);
     if (st_pclass) memcpy(out->pclass, hs + pc_off, n);
     const uint32_t staged = std::min(rows, H);
@@ -2241,14 +2400,18 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
         memcpy(ord->when, hs + when_off, kWhenRow * staged);
         memcpy(ord->exact_until, hs + until_off, kUntilRow * staged);
     }
-    if (rows > H) {   // more rounds than staged: the overflow columns, straight into out
-        const uint32_t e = rows - H;
+    if (caught) (void)cols_copy(ctx, kCatchCols, hs + catch_off, Hc, std::min(recs, Hc), 0, caught, copy_host);
+    if (rows > H || recs > Hc) {   // more than staged: the overflow columns, straight into the caller's arrays
         const auto down = copy_down(s);
-        if ((rc = cols_copy(ctx, kDecideCols, ovf, m, e, H, out, down))) return rc;
-        if (ord) {
-            TCHK(down(ord->when + 8 * (size_t)H, ovf + ovw_off, kWhenRow * e), "decide overflow when");
-            TCHK(down(ord->exact_until + H, ovf + ovu_off, kUntilRow * e), "decide overflow until");
+        if (rows > H) {
+            const uint32_t e = rows - H;
+            if ((rc = cols_copy(ctx, kDecideCols, ovf, m, e, H, out, down))) return rc;
+            if (ord) {
+                TCHK(down(ord->when + 8 * (size_t)H, ovf + ovw_off, kWhenRow * e), "decide overflow when");
+                TCHK(down(ord->exact_until + H, ovf + ovu_off, kUntilRow * e), "decide overflow until");
+            }
         }
+        if (recs > Hc && (rc = cols_copy(ctx, kCatchCols, covf, m, recs - Hc, Hc, caught, down))) return rc;
         TCHK(hipStreamSynchronize(s), "decide overflow sync");
     }
     return HD_OK;
@@ -2256,8 +2419,9 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
 
 // hd_decide and hd_decide_ordered (ord non-NULL and checked by the caller)
 static int decide_host(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in,
-                       hd_decide_out* out, hd_decide_order* ord) {
+                       hd_decide_out* out, hd_decide_order* ord, hd_catch_out* caught = nullptr) {
     if (!ctx || !batch || !verdict || !in || !decide_out_ok(out)) return HD_EINVAL;
+    if (caught) caught->n = 0;
     if (!batch->type || !batch->height || !batch->round || !batch->value32 || !batch->from32) return HD_EINVAL;
     if (in->sched32 && in->n_sched == 0) return HD_EINVAL;
     out->n = 0;
@@ -2288,12 +2452,13 @@ static int decide_host(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdic
         TCHK(hipMemcpyAsync(p, in->value_ok, n, hipMemcpyHostToDevice, ctx->stream), "value_ok upload");
         di.value_ok = p;
     }
-    return hd_decide_run(ctx, &db, d_v, nullptr, di, out, ctx->stream, ord, nullptr);
+    return hd_decide_run(ctx, &db, d_v, nullptr, di, out, ctx->stream, ord, nullptr, caught);
 }
 
 static int decide_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap, const hd_decide_in* in,
-                         hd_decide_out* out, void* stream, hd_decide_order* ord) {
+                         hd_decide_out* out, void* stream, hd_decide_order* ord, hd_catch_out* caught = nullptr) {
     if (!ctx || !dbatch || !in || !decide_out_ok(out)) return HD_EINVAL;
+    if (caught) caught->n = 0;
     if (dbatch->n && (!d_valid_bitmap || !dbatch->type || !dbatch->height || !dbatch->round || !dbatch->value32 ||
                       !dbatch->from32))
         return HD_EINVAL;
@@ -2302,7 +2467,7 @@ static int decide_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_
     if (dbatch->n == 0) return HD_OK;
     (void)hipSetDevice(ctx->device);
     return hd_decide_run(ctx, dbatch, nullptr, d_valid_bitmap, DecideIn{in->f, in->n_sched, in->sched32, in->value_ok},
-                         out, stream ? (hipStream_t)stream : ctx->stream, ord, nullptr);
+                         out, stream ? (hipStream_t)stream : ctx->stream, ord, nullptr, caught);
 }
 
 extern "C" {
@@ -2327,6 +2492,21 @@ int hd_decide_ordered_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const u
                                     void* stream) {
     if (!decide_order_ok(out, order, dbatch ? dbatch->n : 0u)) return HD_EINVAL;
     return decide_bitmap(ctx, dbatch, d_valid_bitmap, in, out, stream, order);
+}
+
+int hd_decide_catch(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in,
+                    hd_decide_out* out, hd_decide_order* order, hd_catch_out* caught) {
+    if (!catch_out_ok(caught)) return HD_EINVAL;
+    if (order && !decide_order_ok(out, order, batch ? batch->n : 0u)) return HD_EINVAL;
+    return decide_host(ctx, batch, verdict, in, out, order, caught);
+}
+
+int hd_decide_catch_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                  const hd_decide_in* in, hd_decide_out* out, hd_decide_order* order,
+                                  hd_catch_out* caught, void* stream) {
+    if (!catch_out_ok(caught)) return HD_EINVAL;
+    if (order && !decide_order_ok(out, order, dbatch ? dbatch->n : 0u)) return HD_EINVAL;
+    return decide_bitmap(ctx, dbatch, d_valid_bitmap, in, out, stream, order, caught);
 }
 
 }  // extern "C"

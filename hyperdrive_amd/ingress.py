@@ -239,20 +239,22 @@ class Ingress:
         self.log = self.v.open_log(self.height, self.f or 0, schedule)
         return self.log
 
-    def flush_decide(self, value_ok=None):
+    def flush_decide(self, value_ok=None, catch=False):
         """flush() followed by one insert of the consumed batch into the open
         log.  Every consumed message is authenticated and admitted, so its
         verdict is VALID.  value_ok stands in for validator.Valid on the
         proposes' values: None (every non-nil value is valid), one byte per
         consumed message, or -- the consumed batch is not known before the
         flush -- a callable that takes the consumed Batch and returns those
-        bytes.  Returns (FlushResult, LogInsertResult)."""
+        bytes.  catch: the insert also returns the catch list of the consumed
+        messages (DecideLog.insert's ``catch``: ``dec.caught``).  Returns
+        (FlushResult, LogInsertResult)."""
         if self.log is None:
             raise RuntimeError("flush_decide without open_log")
         res = self.flush()
         b = res.consumed
         vok = value_ok(b) if callable(value_ok) else value_ok
-        return res, self.log.insert(b, np.zeros(len(b), np.uint8), vok)
+        return res, self.log.insert(b, np.zeros(len(b), np.uint8), vok, catch=catch)
 
     def advance_height(self, height: int) -> None:
         """The Process's own height change after a commit (process.go:710-725:

@@ -254,6 +254,62 @@ class LogInsertResult(OrderedDecideResult):
         return [(i - self.base, h, r, k) for i, h, r, k in self.firings if i >= self.base]
 
 
+# kinds of a catch record (include/hd_verify.h HD_CATCH_*)
+CATCH_NAMES = {1: "double_prevote", 2: "double_precommit", 3: "double_propose", 4: "out_of_turn_propose"}
+
+
+class _Caught:
+    """The catch list of a decide or insert made with ``catch=True``
+    (hd_catch_out): one record per double vote, double propose and out-of-turn
+    propose, in ascending index."""
+
+    @property
+    def caught(self) -> List[Tuple[int, str, int]]:
+        """(index, name, against): the offender, the CATCH_NAMES name of its
+        kind and the logged message it contradicts (WHEN_NEVER for an
+        out-of-turn propose): the arguments of the reference's Catcher calls,
+        in the order of those calls."""
+        return [(int(i), CATCH_NAMES[int(k)], int(a))
+                for i, k, a in zip(self.caught_index, self.caught_kind, self.caught_against)]
+
+
+@dataclass
+class CaughtDecideResult(DecideResult, _Caught):
+    caught_index: np.ndarray = None      # uint32[records], ascending
+    caught_against: np.ndarray = None    # uint32[records]
+    caught_kind: np.ndarray = None       # uint8[records]
+
+
+@dataclass
+class CaughtOrderedDecideResult(OrderedDecideResult, _Caught):
+    caught_index: np.ndarray = None
+    caught_against: np.ndarray = None
+    caught_kind: np.ndarray = None
+
+
+@dataclass
+class CaughtLogInsertResult(LogInsertResult, _Caught):
+    """index and against are joined coordinates, as every index of a
+    LogInsertResult: index - base is the message of this batch; against below
+    base is a log position."""
+    caught_index: np.ndarray = None
+    caught_against: np.ndarray = None
+    caught_kind: np.ndarray = None
+
+
+def _catch_struct(n: int):
+    """An hd_catch_out with room for every message of a batch of n."""
+    from ._lib import HdCatchOut
+    arrs = {"index": np.zeros(max(n, 1), np.uint32), "against": np.zeros(max(n, 1), np.uint32),
+            "kind": np.zeros(max(n, 1), np.uint8)}
+    c = HdCatchOut(n, 0, _ptr(arrs["index"]), _ptr(arrs["against"]), _ptr(arrs["kind"]))
+    return c, arrs
+
+
+def _caught_fields(c, arrs) -> Dict[str, np.ndarray]:
+    return {"caught_" + k: arrs[k][: c.n].copy() for k in ("index", "against", "kind")}
+
+
 class DecideLog:
     """A height's vote and propose logs kept on the device across inserts
     (include/hd_log.h): every insert returns what decide_ordered would return
@@ -331,16 +387,18 @@ class DecideLog:
         info = HdLogInfo(0, 0, 0, _ptr(logpos))
         return o, a, w, when, until, logpos, info
 
-    def _result(self, n, o, a, when, until, logpos, info) -> LogInsertResult:
+    def _result(self, n, o, a, when, until, logpos, info, caught=None) -> LogInsertResult:
         self._rows = o.n
         rows = {k: a[k][: o.n].copy() for k in type(o).ROW_FIELDS}
-        return LogInsertResult(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), when=when[: o.n].copy(),
-                               exact_until=until[: o.n].copy(), base=info.base, kept=info.kept,
-                               logpos=logpos[:n].copy(), relogged=info.relogged, **rows)
+        cls, extra = (CaughtLogInsertResult, _caught_fields(*caught)) if caught else (LogInsertResult, {})
+        return cls(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), when=when[: o.n].copy(),
+                   exact_until=until[: o.n].copy(), base=info.base, kept=info.kept,
+                   logpos=logpos[:n].copy(), relogged=info.relogged, **rows, **extra)
 
-    def insert(self, batch: Batch, verdict: np.ndarray, value_ok=None) -> LogInsertResult:
+    def insert(self, batch: Batch, verdict: np.ndarray, value_ok=None, catch: bool = False) -> LogInsertResult:
         """hd_log_insert of a host batch with its verdicts (and value_ok, one
-        byte per message, as :meth:`Verifier.decide`)."""
+        byte per message, as :meth:`Verifier.decide`).  catch: also return the
+        catch list of this batch (a CaughtLogInsertResult; hd_log_insert_catch)."""
         n = len(batch)
         verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
         if len(verdict) != n:
@@ -350,12 +408,18 @@ class DecideLog:
             raise ValueError("value_ok length mismatch")
         o, a, w, when, until, logpos, info = self._outputs(n)
         cb = batch.c_struct()
+        if catch:
+            c, ca = _catch_struct(n)
+            self._v._check(self._lib.hd_log_insert_catch(self._log, ctypes.byref(cb), _ptr(verdict), _ptr(vok),
+                                                         ctypes.byref(o), ctypes.byref(w), ctypes.byref(info),
+                                                         ctypes.byref(c)), "hd_log_insert_catch")
+            return self._result(n, o, a, when, until, logpos, info, (c, ca))
         self._v._check(self._lib.hd_log_insert(self._log, ctypes.byref(cb), _ptr(verdict), _ptr(vok), ctypes.byref(o),
                                                ctypes.byref(w), ctypes.byref(info)), "hd_log_insert")
         return self._result(n, o, a, when, until, logpos, info)
 
-    def insert_device(self, dbatch: HdBatch, d_bitmap: int, value_ok=None,
-                      stream: Optional[int] = None) -> LogInsertResult:
+    def insert_device(self, dbatch: HdBatch, d_bitmap: int, value_ok=None, stream: Optional[int] = None,
+                      catch: bool = False) -> LogInsertResult:
         """hd_log_insert_device_bitmap over a device batch and the valid bitmap
         of verify_batch_device (bit i is message i of `dbatch`).  value_ok: a
         torch uint8 tensor on the device, or a host array, which is uploaded
@@ -369,6 +433,13 @@ class DecideLog:
         if vok is not None and vok.numel() != n:
             raise ValueError("value_ok length mismatch")
         o, a, w, when, until, logpos, info = self._outputs(n)
+        if catch:
+            c, ca = _catch_struct(n)
+            self._v._check(self._lib.hd_log_insert_catch_device_bitmap(
+                self._log, ctypes.byref(dbatch), d_bitmap, vok.data_ptr() if vok is not None else None,
+                ctypes.byref(o), ctypes.byref(w), ctypes.byref(info), ctypes.byref(c), stream),
+                "hd_log_insert_catch_device_bitmap")
+            return self._result(n, o, a, when, until, logpos, info, (c, ca))
         self._v._check(self._lib.hd_log_insert_device_bitmap(self._log, ctypes.byref(dbatch), d_bitmap,
                                                              vok.data_ptr() if vok is not None else None,
                                                              ctypes.byref(o), ctypes.byref(w), ctypes.byref(info),
@@ -649,17 +720,20 @@ class Verifier:
         return o, arrs
 
     @staticmethod
-    def _decide_result(n: int, o, a) -> DecideResult:
+    def _decide_result(n: int, o, a, caught=None) -> DecideResult:
         rows = {k: a[k][: o.n].copy() for k in type(o).ROW_FIELDS}
-        return DecideResult(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), **rows)
+        cls, extra = (CaughtDecideResult, _caught_fields(*caught)) if caught else (DecideResult, {})
+        return cls(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), **rows, **extra)
 
-    def decide(self, batch: Batch, verdict: np.ndarray, f: int, schedule=None, value_ok=None) -> DecideResult:
+    def decide(self, batch: Batch, verdict: np.ndarray, f: int, schedule=None, value_ok=None,
+               catch: bool = False) -> DecideResult:
         """hd_decide: the vote logs of :meth:`tally`, the propose log of
         process.go:758-819 and every round's eight predicates, on the device.
         schedule: the round-robin order of signatories (rows of 32 bytes) or
         None for no turn check; value_ok: one byte per message standing in for
         validator.Valid on a propose's value (None: every non-nil value is
-        valid)."""
+        valid); catch: also return the catch list (a CaughtDecideResult with
+        ``caught``; hd_decide_catch)."""
         from ._lib import HdDecideIn
         n = len(batch)
         verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
@@ -674,12 +748,17 @@ class Verifier:
         o, a = self._decide_struct(n)
         cin = HdDecideIn(int(f), len(sched) if sched is not None else 0, _ptr(sched), _ptr(vok))
         cb = batch.c_struct()
+        if catch:
+            c, ca = _catch_struct(n)
+            self._check(self._lib.hd_decide_catch(self._ctx, ctypes.byref(cb), _ptr(verdict), ctypes.byref(cin),
+                                                  ctypes.byref(o), None, ctypes.byref(c)), "hd_decide_catch")
+            return self._decide_result(n, o, a, (c, ca))
         self._check(self._lib.hd_decide(self._ctx, ctypes.byref(cb), _ptr(verdict), ctypes.byref(cin),
                                         ctypes.byref(o)), "hd_decide")
         return self._decide_result(n, o, a)
 
     def decide_device(self, dbatch: HdBatch, d_bitmap: int, f: int, schedule=None, value_ok=None,
-                      stream: Optional[int] = None) -> DecideResult:
+                      stream: Optional[int] = None, catch: bool = False) -> DecideResult:
         """hd_decide_device_bitmap over a device batch and the valid bitmap of
         verify_batch_device.  schedule / value_ok: torch tensors on the device
         (uint8 [n_sched, 32] / [n]), or host arrays, which are uploaded first."""
@@ -704,6 +783,13 @@ class Verifier:
         cin = HdDecideIn(int(f), sched.numel() // 32 if sched is not None else 0,
                          sched.data_ptr() if sched is not None else None,
                          vok.data_ptr() if vok is not None else None)
+        if catch:
+            c, ca = _catch_struct(n)
+            self._check(self._lib.hd_decide_catch_device_bitmap(self._ctx, ctypes.byref(dbatch), d_bitmap,
+                                                                ctypes.byref(cin), ctypes.byref(o), None,
+                                                                ctypes.byref(c), stream),
+                        "hd_decide_catch_device_bitmap")
+            return self._decide_result(n, o, a, (c, ca))
         self._check(self._lib.hd_decide_device_bitmap(self._ctx, ctypes.byref(dbatch), d_bitmap, ctypes.byref(cin),
                                                       ctypes.byref(o), stream), "hd_decide_device_bitmap")
         return self._decide_result(n, o, a)
@@ -721,13 +807,14 @@ class Verifier:
         return w, when, until
 
     @staticmethod
-    def _ordered_result(n: int, o, a, when, until) -> OrderedDecideResult:
+    def _ordered_result(n: int, o, a, when, until, caught=None) -> OrderedDecideResult:
         rows = {k: a[k][: o.n].copy() for k in type(o).ROW_FIELDS}
-        return OrderedDecideResult(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), when=when[: o.n].copy(),
-                                   exact_until=until[: o.n].copy(), **rows)
+        cls, extra = (CaughtOrderedDecideResult, _caught_fields(*caught)) if caught else (OrderedDecideResult, {})
+        return cls(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), when=when[: o.n].copy(),
+                   exact_until=until[: o.n].copy(), **rows, **extra)
 
     def decide_ordered(self, batch: Batch, verdict: np.ndarray, f: int, schedule=None,
-                       value_ok=None) -> OrderedDecideResult:
+                       value_ok=None, catch: bool = False) -> OrderedDecideResult:
         """hd_decide_ordered: :meth:`decide` plus the batch index at which each
         round's predicates first hold in batch order (``when``,
         ``exact_until``, ``firings``).  Arguments as :meth:`decide`."""
@@ -746,12 +833,18 @@ class Verifier:
         w, when, until = self._order_struct(n)
         cin = HdDecideIn(int(f), len(sched) if sched is not None else 0, _ptr(sched), _ptr(vok))
         cb = batch.c_struct()
+        if catch:
+            c, ca = _catch_struct(n)
+            self._check(self._lib.hd_decide_catch(self._ctx, ctypes.byref(cb), _ptr(verdict), ctypes.byref(cin),
+                                                  ctypes.byref(o), ctypes.byref(w), ctypes.byref(c)),
+                        "hd_decide_catch")
+            return self._ordered_result(n, o, a, when, until, (c, ca))
         self._check(self._lib.hd_decide_ordered(self._ctx, ctypes.byref(cb), _ptr(verdict), ctypes.byref(cin),
                                                 ctypes.byref(o), ctypes.byref(w)), "hd_decide_ordered")
         return self._ordered_result(n, o, a, when, until)
 
     def decide_ordered_device(self, dbatch: HdBatch, d_bitmap: int, f: int, schedule=None, value_ok=None,
-                              stream: Optional[int] = None) -> OrderedDecideResult:
+                              stream: Optional[int] = None, catch: bool = False) -> OrderedDecideResult:
         """hd_decide_ordered_device_bitmap; arguments as :meth:`decide_device`."""
         import torch
         from ._lib import HdDecideIn
@@ -775,6 +868,13 @@ class Verifier:
         cin = HdDecideIn(int(f), sched.numel() // 32 if sched is not None else 0,
                          sched.data_ptr() if sched is not None else None,
                          vok.data_ptr() if vok is not None else None)
+        if catch:
+            c, ca = _catch_struct(n)
+            self._check(self._lib.hd_decide_catch_device_bitmap(self._ctx, ctypes.byref(dbatch), d_bitmap,
+                                                                ctypes.byref(cin), ctypes.byref(o), ctypes.byref(w),
+                                                                ctypes.byref(c), stream),
+                        "hd_decide_catch_device_bitmap")
+            return self._ordered_result(n, o, a, when, until, (c, ca))
         self._check(self._lib.hd_decide_ordered_device_bitmap(self._ctx, ctypes.byref(dbatch), d_bitmap,
                                                               ctypes.byref(cin), ctypes.byref(o), ctypes.byref(w),
                                                               stream), "hd_decide_ordered_device_bitmap")

@@ -81,6 +81,28 @@ int hd_log_insert_device_bitmap(hd_log* log, const hd_batch* dbatch, const uint3
                                 const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
                                 hd_log_info* info, void* stream);
 
+/* The same inserts plus the catch list (hd_catch_out, hd_verify.h) of this
+ * batch's messages, in joined coordinates like every other index: a record's
+ * index is base + i for message i of this batch; its against is a log position
+ * < base when the logged message was kept by an earlier insert (that call's
+ * logpos named it), and base + j for message j of this batch otherwise.  A
+ * retained entry is never an offender -- it is the only message of its key --
+ * and a conflicting message that a later insert brings again is reported
+ * again, as the reference would catch it again.  An insert of n = 0 has zero
+ * records.  out, order and info are filled exactly as the insert without the
+ * list fills them; out->dup and out->pclass may be NULL.
+ *
+ * HD_EINVAL for a NULL hd_catch_out or cap > 0 with a NULL array; HD_ECAP with
+ * caught->n set to the need when the records do not fit (out->n is set too if
+ * the rows do not fit either); HD_EDEVICE if a record named a retained entry as
+ * its offender.  Like every error these leave the log as it was, so the same
+ * insert repeated with enough room succeeds. */
+int hd_log_insert_catch(hd_log* log, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
+                        hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught);
+int hd_log_insert_catch_device_bitmap(hd_log* log, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                      const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
+                                      hd_log_info* info, hd_catch_out* caught, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

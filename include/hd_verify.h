@@ -31,6 +31,10 @@
  *                       holds when the batch is inserted one message at a
  *                       time (the rules are tried after every insert,
  *                       process.go:229-269).
+ *   hd_decide_catch     either of the two plus the Catcher's calls: each double
+ *                       vote, double propose and out-of-turn propose with the
+ *                       logged message it contradicts (process.go:771-793,
+ *                       838-841, 875-878).
  *   hd_log (hd_log.h)   the same across calls: a height's logs kept on the
  *                       device until the height changes (process.go:710-725).
  *
@@ -580,6 +584,49 @@ int hd_decide_ordered(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict
 int hd_decide_ordered_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
                                     const hd_decide_in* in, hd_decide_out* out, hd_decide_order* order,
                                     void* stream);
+
+/* ---- decide, catch: each offence with the logged message it contradicts ----
+ * The reference reports misbehaviour from inside its inserts: the offender and,
+ * for three of the four calls, the logged message it contradicts
+ * (Catcher.CatchDoublePropose / CatchDoublePrevote / CatchDoublePrecommit /
+ * CatchOutOfTurnPropose, process.go:771-793, 838-841, 875-878).  The catch
+ * list is those calls for a whole batch: one record (index, kind, against)
+ * per message with dup == 2 or pclass 2 or 4, in ascending index -- the order
+ * of the reference's calls, since it inserts one message at a time.
+ *   kind 1, 2  index is a double Prevote / Precommit (dup == 2); against is the
+ *              logged vote of the same (height, round, From): the dup == 0
+ *              message of that key
+ *   kind 3     index is a double propose (pclass == 2); against is the logged
+ *              propose of its round (the row's `propose`)
+ *   kind 4     index is an out-of-turn propose (pclass == 4); against is
+ *              HD_WHEN_NEVER
+ * Identical copies (dup == 1, pclass == 1) have no record.  against < index in
+ * every record that names one.
+ *
+ * hd_decide_catch is hd_decide (order NULL) or hd_decide_ordered (order given)
+ * plus the list: out and order are filled exactly as those calls fill them.
+ * out->dup and out->pclass may be NULL while the list is asked for; neither
+ * is then downloaded.  A votes-only caller passes in->sched32 = NULL.
+ * HD_EINVAL, before any device work, for a NULL hd_catch_out or cap > 0 with
+ * a NULL array (cap == 0 with NULL arrays only counts); HD_ECAP with caught->n
+ * set to the need when n > cap -- if out->cap is too small as well, out->n is
+ * set too.  An empty batch has zero records. */
+#define HD_CATCH_DOUBLE_PREVOTE   1
+#define HD_CATCH_DOUBLE_PRECOMMIT 2
+#define HD_CATCH_DOUBLE_PROPOSE   3
+#define HD_CATCH_OUT_OF_TURN      4
+typedef struct {
+    uint32_t cap;       /* capacity of the arrays (0 with NULL arrays: count only) */
+    uint32_t n;         /* records (the need, when HD_ECAP) */
+    uint32_t* index;    /* ascending */
+    uint32_t* against;  /* HD_WHEN_NEVER for kind 4 */
+    uint8_t*  kind;
+} hd_catch_out;
+int hd_decide_catch(hd_ctx* ctx, const hd_batch* batch, const uint8_t* verdict, const hd_decide_in* in,
+                    hd_decide_out* out, hd_decide_order* order, hd_catch_out* caught);
+int hd_decide_catch_device_bitmap(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                  const hd_decide_in* in, hd_decide_out* out, hd_decide_order* order,
+                                  hd_catch_out* caught, void* stream);
 
 /* ---- multi-GPU in one process ----------------------
  * A context per device plus an RCCL communicator over the devices

@@ -13,6 +13,17 @@ and fed as 16 pieces of 8,000.  Per piece, after warm-up:
   host_votes       hd_votes_insert_batch of the piece into a host table holding
                    the pieces before it (votes only: it knows no proposes)
 
+With --catch the insert is timed twice more (hd_log_insert_catch_device_bitmap):
+
+  insert_catch           the same insert plus the catch list
+  insert_catch_noclass   the same with out->dup and out->pclass NULL: what a
+                         replica that wants only the list pays, against
+                         `insert` with both arrays
+
+--adv P draws the stream from a batch with P % adversarial messages, so that
+there is something to catch (0, the default, repeats messages but never
+conflicts); --only-insert leaves out decide_ordered and host_votes.
+
 Each device call sits between two events on its stream (kernels and the
 download; the call ends in a stream synchronise).  A repetition resets the log
 and feeds the 16 pieces in order, so every piece is timed at the same `base`
@@ -20,7 +31,7 @@ each time.  One JSON line with per-piece medians in milliseconds.  With HD_LIB
 naming an older build only the entry points it has are run, so two builds can
 be compared by running the script once per build in one job.
 
-    python scripts/log_probe.py [--reps 20] [--pieces 16] [--piece 8000]
+    python scripts/log_probe.py [--reps 20] [--pieces 16] [--piece 8000] [--catch] [--adv 0] [--only-insert]
 """
 from __future__ import annotations
 
@@ -49,6 +60,9 @@ def main():
     ap.add_argument("--signers", type=int, default=1000)
     ap.add_argument("--rounds", type=int, default=4)
     ap.add_argument("--label", default=os.environ.get("HD_LIB", "tree"))
+    ap.add_argument("--catch", action="store_true", help="also time the insert with the catch list")
+    ap.add_argument("--adv", type=int, default=0, help="adversarial messages in the source batch, per cent")
+    ap.add_argument("--only-insert", action="store_true", help="leave out decide_ordered and host_votes")
     a = ap.parse_args()
     if a.piece % 32:
         raise SystemExit("log_probe: --piece must be a multiple of 32 (the bitmap is sliced by words)")
@@ -66,7 +80,7 @@ def main():
     v = Verifier(0)
     ks = v.gen_keys(S)
     v.set_signatories(ks[0])
-    src, _, _ = generate(v, 1, distinct, S, 0, keys=ks)
+    src, _, _ = generate(v, 1, distinct, S, a.adv, keys=ks)
     pick = torch.from_numpy(np.random.default_rng(1).integers(0, distinct, n)).cuda()
     db = DeviceBatch(n, *(getattr(src, k)[pick].contiguous() for k in ("type", "height", "round", "valid_round",
                                                                        "value", "frm", "sig")))
@@ -79,7 +93,7 @@ def main():
     for _ in range(2):
         v.verify_batch_device(db.c_struct(), verdict.data_ptr(), None, None, bitmap.data_ptr(), s)
     ws.synchronize()
-    assert int((verdict == 0).sum().item()) == n
+    assert a.adv or int((verdict == 0).sum().item()) == n
     f = quorum.thresholds(S)[0]
     sched = torch.from_numpy(np.ascontiguousarray(ks[0])).cuda()
     torch.cuda.synchronize()
@@ -96,7 +110,7 @@ def main():
         return e0.elapsed_time(e1), (time.perf_counter() - t0) * 1e3
 
     # the piece alone through the one-batch ordered decide
-    if hasattr(lib, "hd_decide_ordered_device_bitmap"):
+    if hasattr(lib, "hd_decide_ordered_device_bitmap") and not a.only_insert:
         cin = _lib.HdDecideIn(f, S, sched.data_ptr(), None)
         o, _oa = v._decide_struct(m)
         w, _when, _until = v._order_struct(m)
@@ -134,33 +148,57 @@ def main():
                     host[k].append(h)
         out.update(base=base, kept=kept, rows=rows, insert_ms=med(dev), insert_host_ms=med(host),
                    entries=log.entries)
+        # the same inserts with the catch list, with and without the class arrays
+        if a.catch and hasattr(lib, "hd_log_insert_catch_device_bitmap"):
+            from hyperdrive_amd.verify import _catch_struct
+            c, _ca = _catch_struct(m)
+            o3, _oa3 = v._decide_struct(m, distinct + m)
+            o3.dup = o3.pclass = None
+            for key, oo in (("insert_catch_ms", o2), ("insert_catch_noclass_ms", o3)):
+                dev, caught = [[] for _ in range(P)], [0] * P
+                for rep in range(a.warm + a.reps):
+                    log.reset(1)
+                    for k, (cs, bm) in enumerate(parts):
+                        def call():
+                            rc = lib.hd_log_insert_catch_device_bitmap(log.handle, ctypes.byref(cs), bm, None,
+                                                                       ctypes.byref(oo), ctypes.byref(w2),
+                                                                       ctypes.byref(info), ctypes.byref(c), s)
+                            assert rc == 0, rc
+                        d, _ = timed(call)
+                        assert info.relogged == info.base
+                        caught[k] = c.n
+                        if rep >= a.warm:
+                            dev[k].append(d)
+                out[key] = med(dev)
+                assert out.setdefault("caught", caught) == caught   # the same records either way
         log.close()
 
-    # the host vote table, accumulating like the log
-    hb = db.to_host()
-    vd = verdict.cpu().numpy()
-    hparts = []
-    for k in range(P):
-        sl = Batch(*(np.ascontiguousarray(x[k * m:(k + 1) * m]) for x in (hb.type, hb.height, hb.round, hb.valid_round,
-                                                                          hb.value, hb.frm, hb.sig)))
-        hparts.append((sl, sl.c_struct(), np.ascontiguousarray(vd[k * m:(k + 1) * m])))
-    st, dbl, ev = np.zeros(m, np.uint8), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
-    ins = ctypes.c_uint32()
-    vl = VoteLog(1)
-    vl.set_f(f)
-    hv = [[] for _ in range(P)]
-    for rep in range(1 + min(a.reps, 5)):
-        lib.hd_votes_reset(vl._v, 1)
-        for k, (_sl, cs, pv) in enumerate(hparts):
-            t0 = time.perf_counter()
-            rc = lib.hd_votes_insert_batch(vl._v, ctypes.byref(cs), pv.ctypes.data, st.ctypes.data, dbl.ctypes.data,
-                                           ev.ctypes.data, ctypes.byref(ins))
-            t1 = time.perf_counter()
-            assert rc == 0, rc
-            if rep:
-                hv[k].append((t1 - t0) * 1e3)
-    vl.close()
-    out["host_votes_ms"] = med(hv)
+    if not a.only_insert:
+        # the host vote table, accumulating like the log
+        hb = db.to_host()
+        vd = verdict.cpu().numpy()
+        hparts = []
+        for k in range(P):
+            sl = Batch(*(np.ascontiguousarray(x[k * m:(k + 1) * m]) for x in (hb.type, hb.height, hb.round, hb.valid_round,
+                                                                              hb.value, hb.frm, hb.sig)))
+            hparts.append((sl, sl.c_struct(), np.ascontiguousarray(vd[k * m:(k + 1) * m])))
+        st, dbl, ev = np.zeros(m, np.uint8), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+        ins = ctypes.c_uint32()
+        vl = VoteLog(1)
+        vl.set_f(f)
+        hv = [[] for _ in range(P)]
+        for rep in range(1 + min(a.reps, 5)):
+            lib.hd_votes_reset(vl._v, 1)
+            for k, (_sl, cs, pv) in enumerate(hparts):
+                t0 = time.perf_counter()
+                rc = lib.hd_votes_insert_batch(vl._v, ctypes.byref(cs), pv.ctypes.data, st.ctypes.data, dbl.ctypes.data,
+                                               ev.ctypes.data, ctypes.byref(ins))
+                t1 = time.perf_counter()
+                assert rc == 0, rc
+                if rep:
+                    hv[k].append((t1 - t0) * 1e3)
+        vl.close()
+        out["host_votes_ms"] = med(hv)
     print(json.dumps(out), flush=True)
     v.close()
 
