@@ -29,6 +29,16 @@ class HostMath:
         L.hdh_verify.argtypes = [ctypes.c_uint32] + [ctypes.c_void_p] * 8 + [ctypes.c_uint32, ctypes.c_int] + \
             [ctypes.c_void_p] * 3
 
+    def mathcheck(self, op: int, inp: np.ndarray) -> np.ndarray:
+        """rows of one single-operation check (include/hd_mathcheck.h) through the host build"""
+        iw, ow = ctypes.c_uint32(), ctypes.c_uint32()
+        assert self.L.hdh_mathcheck_words(op, ctypes.byref(iw), ctypes.byref(ow)) == 0, op
+        inp = np.ascontiguousarray(inp, dtype=np.uint32)
+        assert inp.ndim == 2 and inp.shape[1] == iw.value, (op, inp.shape, iw.value)
+        out = np.zeros((len(inp), ow.value), np.uint32)
+        assert self.L.hdh_mathcheck(op, ctypes.c_uint32(len(inp)), _p(inp), _p(out)) == 0
+        return out
+
     def fe(self, op: str, a: int, b: int = 0):
         out = ctypes.create_string_buffer(33)
         self.L.hdh_fe_op(self.FE_OPS[op], b32(a), b32(b), out)

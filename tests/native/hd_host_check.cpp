@@ -9,8 +9,38 @@
 #include "../../hyperdrive_amd/csrc/hd_scmont.h"
 #include "../../hyperdrive_amd/csrc/hd_keccak.h"
 #include "../../hyperdrive_amd/csrc/hd_modinv.h"
+#include "../../hyperdrive_amd/csrc/hd_mathcheck_ops.h"
 
 using namespace hd;
+
+// The single-operation rows of include/hd_mathcheck.h on the host: the same
+// mc_row<OP> text the gfx950 kernels run (hd_mathcheck_ops.h), row by row.
+// Returns 0, or -1 for an unknown op.
+template <int OP>
+static void mc_rows(uint32_t n, const uint32_t* in, uint32_t* out) {
+    for (uint32_t k = 0; k < n; k++) mc_row<OP>(in + (size_t)k * mc_in_words(OP), out + (size_t)k * mc_out_words(OP));
+}
+extern "C" int hdh_mathcheck_words(int op, uint32_t* in_words, uint32_t* out_words) {
+    *in_words = mc_in_words(op);
+    *out_words = mc_out_words(op);
+    return *in_words && *out_words ? 0 : -1;
+}
+extern "C" int hdh_mathcheck(int op, uint32_t n, const uint32_t* in, uint32_t* out) {
+    switch (op) {
+#define MC(OP) case OP: mc_rows<OP>(n, in, out); return 0;
+        MC(HD_MC_FE_MUL) MC(HD_MC_FE_SQR) MC(HD_MC_FE_NORM_WEAK) MC(HD_MC_FE_NORMALIZE) MC(HD_MC_FE_ADD)
+        MC(HD_MC_FE_SUB2) MC(HD_MC_FE_NEG) MC(HD_MC_FE_MUL_INT) MC(HD_MC_FE_INV) MC(HD_MC_FE_INV_DIVSTEPS)
+        MC(HD_MC_FE_SQRT) MC(HD_MC_FE_FLAGS) MC(HD_MC_FE_SQR_SQR) MC(HD_MC_FE_SQR_MUL_A) MC(HD_MC_FE_SQR_MUL_B)
+        MC(HD_MC_FE_MUL_ALIAS) MC(HD_MC_FE_SQR_N88) MC(HD_MC_SC_MUL) MC(HD_MC_SC_SQR) MC(HD_MC_SC_NEG)
+        MC(HD_MC_SC_ADD) MC(HD_MC_SC_INV) MC(HD_MC_SC_INV_DIVSTEPS) MC(HD_MC_SC_FROM_BE_REDUCE)
+        MC(HD_MC_SC_REDUCE512) MC(HD_MC_SC_SPLIT_LAMBDA) MC(HD_MC_SM_MUL) MC(HD_MC_SM_CHAIN) MC(HD_MC_BOOTH)
+        MC(HD_MC_BOOTH160) MC(HD_MC_FB_DIGITS) MC(HD_MC_GEJ_DBL) MC(HD_MC_GEJ_ADD_GE) MC(HD_MC_GEJ_ADD)
+        MC(HD_MC_GEJ_ADD_GE_NX) MC(HD_MC_GEJ_ADD_GE_Z1) MC(HD_MC_GXZ_ADD_GE_NX) MC(HD_MC_GXZ_ADD_GE_Z1)
+        MC(HD_MC_GXZ_CHAIN)
+#undef MC
+        default: return -1;
+    }
+}
 
 static ge g_tab[2 * HD_GLV_GTAB_N];
 static bool g_init = false;
