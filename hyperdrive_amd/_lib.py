@@ -258,6 +258,8 @@ SIGNATURES = {
     "hd_mathcheck_words": (ctypes.c_int, [ctypes.c_int, c_u32p, c_u32p]),
     "hd_mathcheck": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_void_p,
                                     ctypes.c_void_p]),
+    "hd_fb_table_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint32,
+                                        ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), c_u32p, ctypes.c_void_p]),
     # include/hd_codec.h
     "hd_record_size": (ctypes.c_uint32, [ctypes.c_int, ctypes.c_int]),
     "hd_unmarshal_batch_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,

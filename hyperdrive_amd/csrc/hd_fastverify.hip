@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "../../include/hd_verify.h"
+#include "../../include/hd_mathcheck.h"
 #include "hd_fixedbase.h"
 #include "hd_dedup.h"
 #include "hd_scmont.h"
@@ -2338,6 +2339,65 @@ int hd_ctx_overlap_stats(hd_ctx* ctx, uint32_t* capped, uint32_t* lean, uint32_t
     if (capped) *capped = f ? f->n_capped : 0;
     if (lean) *lean = f ? f->n_lean : 0;
     if (chained) *chained = f ? f->n_chained : 0;
+    return HD_OK;
+}
+
+// Test surface only (include/hd_mathcheck.h): table entries as the builder
+// left them, copied to the host.  No kernel, nothing queued: the call waits
+// for the context's work and reads.
+int hd_fb_table_read(hd_ctx* ctx, int32_t which, uint64_t first, uint32_t count, uint8_t* out64, int* width,
+                     uint32_t* state, uint8_t* key64) {
+    if (!ctx || !ctx->fb || which < -1 || (count && !out64)) return HD_EINVAL;
+    (void)hipSetDevice(ctx->device);
+    FbWork* f = ctx->fb;
+    int rq = hd_fb_quiesce(ctx);
+    if (rq) return rq;
+    FBCHK(hipStreamSynchronize(ctx->stream), "table read sync");
+    const gp* tab = nullptr;
+    uint64_t entries = 0;
+    uint32_t st = HD_FB_READY;
+    int w = HD_FB_WG;
+    gp key;
+    if (which < 0) {
+        ge g;
+        const uint32_t GX[8] = {0x79BE667Eu, 0xF9DCBBACu, 0x55A06295u, 0xCE870B07u,
+                                0x029BFCDBu, 0x2DCE28D9u, 0x59F2815Bu, 0x16F81798u};
+        const uint32_t GY[8] = {0x483ADA77u, 0x26A3C465u, 0x5DA4FBFCu, 0x0E1108A8u,
+                                0xFD17B448u, 0xA6855419u, 0x9C47D08Fu, 0xFB10D4B8u};
+        fe_from_be(g.x, GX);
+        fe_from_be(g.y, GY);
+        gp_pack(key, g);
+        tab = f->gtab;
+        entries = FbL<HD_FB_WG>::TAB;
+        if (!tab) return HD_EINVAL;
+    } else {
+        if ((uint32_t)which >= ctx->n_adm || !f->adm_slot || !f->map_ok) return HD_EINVAL;
+        int32_t slot = -1;
+        FBCHK(hipMemcpy(&slot, f->adm_slot + which, 4, hipMemcpyDeviceToHost), "slot read");
+        if (slot < 1 || (uint32_t)slot >= f->nslots) return HD_EINVAL;   // over the slot cap: no table
+        w = f->wp;
+        entries = fb_tab_entries(w);
+        FBCHK(hipMemcpy(&st, f->state + slot, 4, hipMemcpyDeviceToHost), "state read");
+        gp* t = nullptr;
+        FBCHK(hipMemcpy(&t, f->tabs + slot, sizeof(gp*), hipMemcpyDeviceToHost), "table pointer read");
+        tab = t;
+        memset(&key, 0, sizeof(key));
+        if (st == HD_FB_LEARNED || st == HD_FB_READY) {
+            ge p;
+            FBCHK(hipMemcpy(&p, f->pub + slot, sizeof(ge), hipMemcpyDeviceToHost), "key read");
+            fe_normalize(p.x);
+            fe_normalize(p.y);
+            gp_pack(key, p);
+        }
+    }
+    if (width) *width = w;
+    if (state) *state = st;
+    if (key64) memcpy(key64, &key, 64);
+    if (first > entries || count > entries - first) return HD_EINVAL;
+    if (count && st == HD_FB_READY) {
+        if (!tab) return HD_EINVAL;
+        FBCHK(hipMemcpy(out64, tab + first, sizeof(gp) * (size_t)count, hipMemcpyDeviceToHost), "table read");
+    }
     return HD_OK;
 }
 

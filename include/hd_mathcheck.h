@@ -79,6 +79,23 @@ int hd_mathcheck_words(int op, uint32_t* in_words, uint32_t* out_words);
 /* runs op over n rows (1 <= n <= HD_MC_MAX_ROWS) in blocks of `block` threads
  * (64 or 256); in and out are host arrays of n rows */
 int hd_mathcheck(int device, int op, uint32_t n, int block, const uint32_t* in, uint32_t* out);
+
+/* The fixed-base tables as the device built them (tests/test_gpu_fb_tables.py).
+ * Test surface only, read-only: no kernel, nothing queued, nothing in the
+ * product calls it.
+ * which = -1: the device's G table; which >= 0: the table of the admitted
+ * signatory with that index in the sorted admitted set.  Waits for the
+ * context's verify calls and table builds, then copies entries
+ * [first, first + count) to out64, 64 bytes each (x, y as 8 little-endian
+ * words).  *width = window bits, *state = the slot's state (0 empty, 1 claimed,
+ * 2 key learned, 3 table ready; 3 for G), key64 = the slot's key in the same
+ * 64-byte layout (G for which = -1; zeros while no key is known).  A slot that
+ * is not ready copies nothing.  count == 0 returns width / state / key only.
+ * Any of width, state, key64 may be NULL.  HD_EINVAL for a range outside the
+ * table or an index without a slot. */
+struct hd_ctx;
+int hd_fb_table_read(struct hd_ctx* ctx, int32_t which, uint64_t first, uint32_t count, uint8_t* out64,
+                     int* width, uint32_t* state, uint8_t* key64);
 #ifdef __cplusplus
 }
 #endif

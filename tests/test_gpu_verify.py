@@ -569,3 +569,184 @@ def test_zero_window_digits_vs_oracle(gpu, oracle, key_width):
                     assert v.fastpath_stats()[1] == n // 2, rnd   # only the mismatching Froms fall back
     finally:
         v.close()
+
+
+NOT_AUTHENTIC = 8
+
+
+def _edge_digit_rows(oracle, S, key_width, g_width):
+    """Signatures whose known-key check reads the table entries that random
+    scalars essentially never reach (fb_table_ref.edge_digit_scalars: the
+    extreme digits +-2^(W-1), the top window's maximum and maximum - 1, and
+    1, 2, 32, 33, 512, 513), by _zero_digit_rows' recipe with the digest
+    supplied: u2 carries the digits at the key width (the key tables), u1 at
+    the G width (the G table), the other scalar is random.  Each pair is sent
+    honestly and with a mismatching From."""
+    import random
+    import fb_table_ref as R
+    from math_cases import fb_digits_ref
+    O = oracle
+    keys = O.KeyCache()
+    rng = random.Random(1000 + key_width)
+    pairs = []
+    for u2, want, top in R.edge_digit_scalars(key_width, rng):
+        R.assert_digits(u2, key_width, want, top, fb_digits_ref)
+        pairs.append((rng.randrange(1, O.N), u2))
+    for u1, want, top in R.edge_digit_scalars(g_width, rng):
+        R.assert_digits(u1, g_width, want, top, fb_digits_ref)
+        pairs.append((u1, rng.randrange(1, O.N)))
+    rows, digests = [], []
+    for j, (u1, u2) in enumerate(pairs):
+        signer = j % S
+        d = keys.sk(signer)
+        k = (u1 + u2 * d) % O.N
+        R_ = O.point_mul(k, O.G)
+        r = R_[0] % O.N
+        v = (R_[1] & 1) | (2 if R_[0] >= O.N else 0)
+        s = r * pow(u2, -1, O.N) % O.N
+        m = u1 * s % O.N
+        assert m * pow(s, -1, O.N) % O.N == u1 and r * pow(s, -1, O.N) % O.N == u2
+        sig = r.to_bytes(32, "big") + s.to_bytes(32, "big") + bytes([v])
+        val = bytes(rng.randrange(256) for _ in range(32))
+        for claimed in (signer, (signer + 1) % S):   # honest, then a mismatching From
+            rows.append((O.PREVOTE, 1 + j, 0, -1, val, keys.signatory(claimed), sig))
+            digests.append(m.to_bytes(32, "big"))
+    return rows, digests, keys
+
+
+def _g_width(v):
+    import ctypes
+    from hyperdrive_amd import _lib
+    w = ctypes.c_int(0)
+    assert _lib.load().hd_fb_table_read(v.handle, -1, 0, 0, None, ctypes.byref(w), None, None) == 0
+    return w.value
+
+
+@pytest.mark.parametrize("key_width", [13, 16, 20, 22])
+def test_edge_window_digits_vs_oracle(gpu, oracle, key_width):
+    """The table entries at the edges of the builder's walk, read through the
+    product kernels: messages whose u2 (at every key width) and u1 (at the G
+    width) have the digits -2^(W-1) and +2^(W-1) in a low, the middle and the
+    last full window, the top window's maximum and maximum - 1, and 1, 2, 32,
+    33, 512, 513.  Verdicts and recovered signatories equal the oracle's
+    recovery through the full recovery (pass 1) and the known-key check
+    (passes 2, 3), where exactly the mismatching Froms fall back: a wrong
+    entry would send an honest message to the fallback too."""
+    import torch
+    from hyperdrive_amd.device import DeviceBatch, work_stream
+    from hyperdrive_amd.digest import verify_digest_device
+    from hyperdrive_amd.verify import Batch
+    O = oracle
+    S = 4
+    v = gpu.Verifier(0)
+    try:
+        rows, digests, keys = _edge_digit_rows(O, S, key_width, _g_width(v))
+        want, wrec = [], []
+        for (t, h, r, vr, val, frm, sig), dg in zip(rows, digests):
+            verdict, Q = O.recover(dg, sig)
+            if verdict == O.VALID:
+                got = O.signatory_of_pub(Q, True)
+                verdict = O.VALID if got == frm else O.SIGNATORY_MISMATCH
+                wrec.append(got)
+            else:
+                wrec.append(bytes(32))
+            want.append(verdict)
+        assert want == [O.VALID, O.SIGNATORY_MISMATCH] * (len(rows) // 2) and len(rows) == 2 * 28
+        v.set_variant("key_width", key_width)
+        v.set_signatories(np.frombuffer(b"".join(keys.signatory(k) for k in range(S)), np.uint8).reshape(S, 32))
+        b = Batch.from_lists(*[[x[k] for x in rows] for k in range(7)])
+        ws = work_stream()
+        with torch.cuda.stream(ws):
+            db = DeviceBatch.from_host(b)
+            dg = torch.from_numpy(np.frombuffer(b"".join(digests), np.uint8).reshape(-1, 32).copy()).cuda()
+            n = len(rows)
+            for rnd in range(3):
+                vd = torch.full((n,), 9, dtype=torch.uint8, device="cuda")
+                rec = torch.zeros((n, 32), dtype=torch.uint8, device="cuda")
+                verify_digest_device(v, db, dg, vd.data_ptr(), rec.data_ptr(), stream=ws)
+                ws.synchronize()
+                assert vd.cpu().tolist() == want, rnd
+                assert rec.cpu().numpy().tobytes() == b"".join(wrec), rnd
+                if rnd > 0:
+                    assert v.fastpath_stats() == (S, n // 2), rnd   # only the mismatching Froms fall back
+    finally:
+        v.close()
+
+
+def _fitted_key_rows(oracle, key_width, g_width):
+    """Ordinary messages (the digest is the message's own SHA-256, as
+    hd_authenticate_batch_device computes it) whose known-key check still
+    reads the edge entries: with the digest m fixed, one of u1 = m / s,
+    u2 = r / s is chosen and the signing key is fitted to it -- k random,
+    R = k G, r = R.x, s = r / u2 (or m / u1), d = (s k - m) / r.  One key per
+    scalar, so the digits come packed into two scalars per table
+    (fb_table_ref.combined_digit_scalars): two keys whose u2 carries them at
+    the key width, two whose u1 carries them at the G width.  Each message is
+    sent honestly and with the From of the next fitted key."""
+    import random
+    import fb_table_ref as R
+    from math_cases import fb_digits_ref
+    O = oracle
+    rng = random.Random(2000 + key_width)
+    targets = [("u2", key_width, t) for t in R.combined_digit_scalars(key_width, rng)]
+    targets += [("u1", g_width, t) for t in R.combined_digit_scalars(g_width, rng)]
+    signed = []
+    for j, (which, w, (t, want, top)) in enumerate(targets):
+        val = bytes(rng.randrange(256) for _ in range(32))
+        dg = O.message_digest(O.PRECOMMIT, 3 + j, 1, -1, val)
+        m = int.from_bytes(dg, "big") % O.N
+        k = rng.randrange(1, O.N)
+        R_ = O.point_mul(k, O.G)
+        r = R_[0] % O.N
+        v = (R_[1] & 1) | (2 if R_[0] >= O.N else 0)
+        s = (r if which == "u2" else m) * pow(t, -1, O.N) % O.N
+        d = (s * k - m) * pow(r, -1, O.N) % O.N
+        assert 0 < d < O.N and 0 < s < O.N
+        sinv = pow(s, -1, O.N)
+        R.assert_digits((r if which == "u2" else m) * sinv % O.N, w, want, top, fb_digits_ref)
+        sig = r.to_bytes(32, "big") + s.to_bytes(32, "big") + bytes([v])
+        signatory = O.signatory_of_pub(O.pubkey_of(d), True)
+        signed.append((O.PRECOMMIT, 3 + j, 1, -1, val, signatory, sig))
+    rows = []
+    for j, row in enumerate(signed):
+        rows.append(row)
+        rows.append(row[:5] + (signed[(j + 1) % len(signed)][5],) + row[6:])
+    return rows, [x[5] for x in signed]
+
+
+@pytest.mark.parametrize("key_width", [13, 16, 20, 22])
+def test_edge_window_digits_authenticate(gpu, oracle, key_width):
+    """hd_authenticate_batch_device, where a failed known-key comparison is
+    final: once the keys are READY every honest message whose scalars read the
+    edge entries is VALID and every one with another signatory's From is
+    NOT_AUTHENTIC.  A wrong table entry would drop the honest message here
+    instead of sending it to the full recovery."""
+    import torch
+    from hyperdrive_amd.device import DeviceBatch, work_stream
+    from hyperdrive_amd.verify import Batch
+    O = oracle
+    v = gpu.Verifier(0)
+    try:
+        rows, admitted = _fitted_key_rows(O, key_width, _g_width(v))
+        want = [O.verify_message(*row, set(admitted)) for row in rows]
+        want = [x[0] if isinstance(x, tuple) else x for x in want]
+        assert want == [O.VALID, O.SIGNATORY_MISMATCH] * len(admitted)
+        v.set_variant("key_width", key_width)
+        v.set_signatories(np.frombuffer(b"".join(admitted), np.uint8).reshape(len(admitted), 32))
+        b = Batch.from_lists(*[[x[k] for x in rows] for k in range(7)])
+        ws = work_stream()
+        with torch.cuda.stream(ws):
+            db = DeviceBatch.from_host(b)
+            n = len(rows)
+            for rnd in range(3):
+                out = torch.full((n,), 255, dtype=torch.uint8, device="cuda")
+                v.authenticate_batch_device(db.c_struct(), out.data_ptr(), ws.cuda_stream)
+                ws.synchronize()
+                if rnd == 0:
+                    assert out.cpu().tolist() == want             # no key known yet: the full recovery
+                    assert v.fastpath_stats()[0] == len(admitted)
+                else:
+                    assert out.cpu().tolist() == [O.VALID, NOT_AUTHENTIC] * len(admitted), rnd
+                    assert v.fastpath_stats()[1] == 0, rnd        # decided by the known-key check alone
+    finally:
+        v.close()
