@@ -113,7 +113,7 @@ struct FbWork {
     // concurrent call's k_fast_sums).  UINT32_MAX = none seen yet.
     // [2], [3]: the distinct live messages and the batch size of the latest
     // call (k_fast_sinv stores them); their ratio picks the next calls'
-    // messages per inversion (split_k_for).
+    // messages per inversion (fb_plan_call; a call reads the four once).
     uint32_t* est_host = nullptr;
     uint32_t* est_dev = nullptr;
     // hd_ctx_dedup_stats: [0] messages that entered the known-key check, [1]
@@ -136,16 +136,32 @@ struct FbWork {
     // HD_VAR_SUM_CHAIN: a call's k_fast_sums waits for the previous call's
     // when that call launched one on another stream, so one call's sums runs
     // at a time and the other calls' short kernels run beside it instead of
-    // in lockstep with each other.  sums_done is recorded right after a
-    // chained launch; sums_prev says that the previous call recorded it (a
+    // in lockstep with each other.  done is recorded right after a
+    // chained launch; prev says that the previous call recorded it (a
     // call without a launch -- no admitted set, an early error return --
     // leaves it false, and the next call does not wait).  A wait only ever
     // names work submitted earlier, so the order between calls stays acyclic.
     // The event is older than the call events (done, Scratch::done) of its
     // call, so whoever waits for those has waited for it.
-    hipEvent_t sums_done = nullptr;
-    hipStream_t sums_last = nullptr;
-    bool sums_prev = false, sums_now = false;
+    struct SumsChain {
+        hipEvent_t done = nullptr;
+        hipStream_t last = nullptr;
+        bool prev = false, now = false;
+        // start of a call: what the previous call launched; this call has
+        // launched nothing yet, whichever way it returns
+        void begin_call() { prev = now; now = false; }
+        // before a chained call's sums: whether s was made to wait.  Without
+        // the event (creation failed) the call runs unchained.
+        bool wait(hipStream_t s) {
+            if (!done && hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) done = nullptr;
+            return done && prev && last != s && hipStreamWaitEvent(s, done, 0) == hipSuccess;
+        }
+        // after a chained call's sums
+        void record(hipStream_t s) {
+            now = done && hipEventRecord(done, s) == hipSuccess;
+            if (now) last = s;
+        }
+    } sums;
     uint32_t n_capped = 0, n_lean = 0, n_chained = 0;   // hd_ctx_overlap_stats
     // hd_ctx_profile: event pairs around whole calls and around k_fast_sums
     bool prof = false;
@@ -155,7 +171,7 @@ struct FbWork {
     std::vector<uint32_t> free_slots;
     uint32_t used = 1;            // slots handed out so far (slot 0 = G)
     int wp = HD_FB_W;             // window width of the per-key tables (HD_FB_W or HD_FB_WW)
-    int last_k = 8;               // messages per inversion of the last split check (split_k_for)
+    int last_k = 8;               // messages per inversion of the last split check (FbCallPlan::k)
     double budget = 0;            // table bytes allowed (HD_FB_MAX_BYTES), shared per device
     size_t bytes = 0;             // table bytes this context holds
     // Foreign keys (HD_VAR_FOREIGN_KEYS): fres slots fbase .. reserved once
@@ -608,7 +624,7 @@ __global__ __launch_bounds__(256) void k_fast_sinv(uint32_t n, SplitRows rows, u
     const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
     if (t == 0) {
         const uint32_t reps = rows.cnt[3];
-        if (est) {   // the call's slots, then its n (read in this order by split_k_for's share)
+        if (est) {   // the call's slots, then its n (read in this order by fb_verify_impl's snapshot)
             est[1] = n;
             est[0] = nc;
         }
@@ -1301,18 +1317,26 @@ __global__ void k_fb_ready(const uint32_t* __restrict__ list, const uint32_t* __
     }
 }
 
+// f(std::integral_constant) over the compiled per-key table widths (any other
+// wp: HD_FB_W) and over the messages per inversion (8 unless 16)
+template <typename F>
+static auto with_width(int wp, F f) {
+    if (wp == HD_FB_WX) return f(std::integral_constant<int, HD_FB_WX>{});
+    if (wp == HD_FB_WW) return f(std::integral_constant<int, HD_FB_WW>{});
+    if (wp == HD_FB_WN) return f(std::integral_constant<int, HD_FB_WN>{});
+    return f(std::integral_constant<int, HD_FB_W>{});
+}
+template <typename F>
+static auto with_k(int k, F f) {
+    return k == 16 ? f(std::integral_constant<int, 16>{}) : f(std::integral_constant<int, 8>{});
+}
+
 // per-key table geometry of width wp
 size_t fb_tab_entries(int wp) {
-    return wp == HD_FB_WX   ? FbL<HD_FB_WX>::TAB
-           : wp == HD_FB_WW ? FbL<HD_FB_WW>::TAB
-           : wp == HD_FB_WN ? FbL<HD_FB_WN>::TAB
-                            : FbL<HD_FB_W>::TAB;
+    return with_width(wp, [](auto w) { return (size_t)FbL<decltype(w)::value>::TAB; });
 }
 int fb_nwin(int wp) {
-    return wp == HD_FB_WX   ? FbL<HD_FB_WX>::NWIN
-           : wp == HD_FB_WW ? FbL<HD_FB_WW>::NWIN
-           : wp == HD_FB_WN ? FbL<HD_FB_WN>::NWIN
-                            : FbL<HD_FB_W>::NWIN;
+    return with_width(wp, [](auto w) { return (int)FbL<decltype(w)::value>::NWIN; });
 }
 double fb_slot_bytes(int wp) {
     return (double)sizeof(gp) * (double)fb_tab_entries(wp) + (double)sizeof(ge) * (fb_nwin(wp) + 1) + 8;
@@ -1409,19 +1433,11 @@ int fb_learn(hd_ctx* ctx, hipStream_t s) {
     f->fforce = false;
     const uint32_t g = (uint32_t)std::max(ctx->n_cu, 1) * 4u;
     k_fb_list<<<1, 256, 0, s>>>(f->nslots, f->state, f->list, f->counts);
-    if (f->wp == HD_FB_WX) {
-        k_fb_bases<HD_FB_WX><<<g, 256, 0, s>>>(f->list, f->counts, f->pub, f->base);
-        k_fb_runs<HD_FB_WX><<<fb_run_blocks(ctx), 256, 0, s>>>(f->list, f->counts, f->base, f->tabs, f->zr);
-    } else if (f->wp == HD_FB_WW) {
-        k_fb_bases<HD_FB_WW><<<g, 256, 0, s>>>(f->list, f->counts, f->pub, f->base);
-        k_fb_runs<HD_FB_WW><<<fb_run_blocks(ctx), 256, 0, s>>>(f->list, f->counts, f->base, f->tabs, f->zr);
-    } else if (f->wp == HD_FB_WN) {
-        k_fb_bases<HD_FB_WN><<<g, 256, 0, s>>>(f->list, f->counts, f->pub, f->base);
-        k_fb_runs<HD_FB_WN><<<fb_run_blocks(ctx), 256, 0, s>>>(f->list, f->counts, f->base, f->tabs, f->zr);
-    } else {
-        k_fb_bases<HD_FB_W><<<g, 256, 0, s>>>(f->list, f->counts, f->pub, f->base);
-        k_fb_runs<HD_FB_W><<<fb_run_blocks(ctx), 256, 0, s>>>(f->list, f->counts, f->base, f->tabs, f->zr);
-    }
+    with_width(f->wp, [&](auto w) {
+        constexpr int WP = decltype(w)::value;
+        k_fb_bases<WP><<<g, 256, 0, s>>>(f->list, f->counts, f->pub, f->base);
+        k_fb_runs<WP><<<fb_run_blocks(ctx), 256, 0, s>>>(f->list, f->counts, f->base, f->tabs, f->zr);
+    });
     k_fb_ready<<<1, 256, 0, s>>>(f->list, f->counts, f->state, f->nr_dev, f->fbase, f->fbase + f->fres);
     FBCHK(hipGetLastError(), "fb table kernels");
     return HD_OK;
@@ -1655,7 +1671,7 @@ void hd_fb_release(hd_ctx* ctx) {
     FbWork* f = ctx->fb;
     fb_free_tables(ctx);
     if (f->done) (void)hipEventDestroy(f->done);
-    if (f->sums_done) (void)hipEventDestroy(f->sums_done);
+    if (f->sums.done) (void)hipEventDestroy(f->sums.done);
     for (hipEvent_t e : f->ev_call) (void)hipEventDestroy(e);
     for (hipEvent_t e : f->ev_sums) (void)hipEventDestroy(e);
     for (auto& sc : f->sc) {
@@ -1672,36 +1688,6 @@ void hd_fb_release(hd_ctx* ctx) {
     if (f->fpend_host) (void)hipHostFree(f->fpend_host);
     delete f;
     ctx->fb = nullptr;
-}
-
-// Messages per inversion of the known-key check (HD_VAR_SPLIT_K): 8 or 16;
-// -1 (default) by size: 16 from 2^19 expected slots up, else 8 (before
-// round 7: from 2^20 - 2^16 messages up, 65,536 lanes, one wave per SIMD).  The inversion kernels are bound by their
-// dependent ALU chains; halving the inversions outweighs the lost second wave
-// per SIMD (1M C2 messages, one box, scalars and prefixes in registers:
-// k_fast_sinv 102 -> 91 us, k_fast_zinv 91 -> 76 us from K = 8 to 16; with the
-// rows in HBM between steps K = 4 / 8 / 16 gave 177 / 111 / 90 and 166 / 102
-// / 85 us)
-// The lanes are the distinct live messages, not the batch (repeats take no
-// slot).  The rule looks at this call's n times the slot share of the latest
-// finished call (its slots and its n, which k_fast_sinv stores into pinned
-// memory: no host sync), so a call of another size after it is still judged
-// by its own size.  Any K is correct; a stale share only picks the other one.
-// Before any call has finished the share is 1.
-static int split_k_for(const hd_ctx* ctx, uint32_t n) {
-    const int k = ctx->var[HD_VAR_SPLIT_K];
-    if (k > 0) return k;
-    uint64_t lanes = n;
-    if (const volatile uint32_t* est = ctx->fb->est_host) {
-        const uint32_t seen = est[2], of = est[3];
-        // (a call in which nothing entered the check -- keys still unknown -- says nothing about the share)
-        if (seen != 0xFFFFFFFFu && of != 0xFFFFFFFFu && seen != 0 && seen <= of) lanes = (uint64_t)n * seen / of;
-    }
-    // Round 7, C2 with repeats merged (~623k slots, 609 waves at K = 16): K = 16
-    // 1,063 M msgs/s against 1,044-1,048 M at K = 8, so the rule's threshold
-    // came down from 2^20 - 2^16 to 2^19 slots; C3's 128k messages measured
-    // K = 8 faster (round 6), and nothing between the two has been measured.
-    return lanes >= (1u << 19) ? 16 : 8;
 }
 
 // Per-key window width for an admitted set of m: the widest tables
@@ -1915,48 +1901,6 @@ static hipEvent_t* fb_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, bool 
     return &ev[2 * used++];
 }
 
-// Blocks of a grid-stride fallback kernel (k_slow_lift, k_verify over a
-// list) for the latest list length seen (FbWork::est_host): 1.25x its
-// blocks, at least 64 (a sudden burst of leftovers costs a few grid-stride
-// rounds once), at most `full`.
-static uint32_t fallback_blocks(uint32_t est, uint32_t full) {
-    if (est == 0xFFFFFFFFu) return full;
-    const uint64_t want = ((uint64_t)est * 5 / 4 + 255) / 256;
-    return (uint32_t)std::min<uint64_t>(full, std::max<uint64_t>(want, std::min(64u, full)));
-}
-
-// k_fast_sums waves per SIMD for a batch of n (HD_VAR_SUM_WAVES).
-// 0 (the default): 4 waves per SIMD for a batch that fills fewer than two
-// rounds at 3 (C3's 128k messages: +5 %; measured 3 % slower per 1M, where
-// 3 waves keep the loaded-ahead table points)
-static int sums_waves(const hd_ctx* ctx, uint32_t n) {
-    const int w = ctx->var[HD_VAR_SUM_WAVES];
-    if (w) return w;
-    return (uint64_t)n < 2ull * 3 * 4 * 64 * (uint64_t)std::max(ctx->n_cu, 1) ? 4 : 3;
-}
-
-// Whether a call of n messages takes the overlap path (HD_VAR_SUM_CAP,
-// HD_VAR_LEAN_INV, HD_VAR_SUM_CHAIN, each where its variant is on): not with
-// the 4-wave sums (small batches), and not while the latest call left more
-// than 1 / 128 of its size over from the known-key check (FbWork::est_host[0]; none
-// seen yet counts as none).  Those recoveries' waves sit on the SIMDs for
-// more than a sums' length, and with one capped sums at a time the chip runs
-// short of work beside them: C5 (30 % adversarial) measured 10 % slower on
-// the overlap path, so such traffic keeps the path without it (DESIGN 5,
-// round 12).  Authentication calls (the ingress, whose pushes alternate with
-// the message queue's many short kernels) keep that path too: the ingress
-// line measured 1-8 % slower on the overlap path in three pairs of runs.
-// Evaluated once per call, when it is submitted (fb_verify_impl), and handed
-// down.  The estimate is pinned memory the device writes as earlier calls
-// run, so which path a call takes -- its speed, never its outputs -- depends
-// on how far those calls have come and is not reproducible from run to run
-// while calls with many leftovers are in flight.
-static bool sums_overlap(const hd_ctx* ctx, uint32_t n) {
-    if (sums_waves(ctx, n) == 4) return false;
-    const uint32_t est = ctx->fb->est_host ? *(volatile uint32_t*)ctx->fb->est_host : 0xFFFFFFFFu;
-    return est == 0xFFFFFFFFu || (uint64_t)est * 128 <= n;
-}
-
 // HD_VAR_SUM_CAP: the dynamic LDS that holds the 3-wave k_fast_sums at two
 // 256-lane blocks per CU (two waves per SIMD, 2 x 168 of its 512 VGPRs; 176
 // stay free for other kernels' waves).  A block reserves HD_SUMS_CAP_LDS in
@@ -1975,21 +1919,18 @@ static constexpr size_t sums_cap_lds() {
     return HD_SUMS_CAP_LDS - stat;
 }
 
-// k_fast_sums occupancy (sums_waves), prefetch depth (HD_VAR_SUM_PREFETCH)
-// and residency cap (HD_VAR_SUM_CAP: the 3-wave forms only)
+// the plan's k_fast_sums form (occupancy and prefetch depth), the 3-wave
+// forms with the residency cap where the plan says so
 template <int WP>
-static void launch_sums(const hd_ctx* ctx, uint32_t blocks, hipStream_t s, uint32_t n, const gp* gtab,
-                        const gp* const* tab, const SplitRows& rows, bool overlap) {
-    const int w = sums_waves(ctx, n);
-    const int pf = ctx->var[HD_VAR_SUM_PREFETCH];
-    const size_t cap = ctx->var[HD_VAR_SUM_CAP] && overlap && w == 3 ? sums_cap_lds<WP>() : 0;
-    if (cap) ctx->fb->n_capped++;
-    if (pf == 2) {
-        if (w == 2) k_fast_sums<2, WP, 2><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
-        else k_fast_sums<3, WP, 2><<<blocks, 256, cap, s>>>(n, gtab, tab, rows);   // (no 4-wave form)
+static void launch_sums(const FbCallPlan& p, uint32_t blocks, hipStream_t s, uint32_t n, const gp* gtab,
+                        const gp* const* tab, const SplitRows& rows) {
+    const size_t cap = p.capped ? sums_cap_lds<WP>() : 0;
+    if (p.sums_pf == 2) {
+        if (p.sums_waves == 2) k_fast_sums<2, WP, 2><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
+        else k_fast_sums<3, WP, 2><<<blocks, 256, cap, s>>>(n, gtab, tab, rows);
     } else {
-        if (w == 2) k_fast_sums<2, WP, 1><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
-        else if (w == 4) k_fast_sums<4, WP, 0><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
+        if (p.sums_waves == 2) k_fast_sums<2, WP, 1><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
+        else if (p.sums_waves == 4) k_fast_sums<4, WP, 0><<<blocks, 256, 0, s>>>(n, gtab, tab, rows);
         else k_fast_sums<3, WP, 1><<<blocks, 256, cap, s>>>(n, gtab, tab, rows);
     }
 }
@@ -1997,7 +1938,7 @@ static void launch_sums(const hd_ctx* ctx, uint32_t blocks, hipStream_t s, uint3
 template <int K, int WP>
 static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_t* d_verdict,
                          uint8_t* d_rec32, int32_t* d_signer, uint32_t* d_bitmap, const SplitRows& rows,
-                         const FbWork::Scratch& sc, hipStream_t s, bool auth, bool share, bool overlap) {
+                         const FbWork::Scratch& sc, hipStream_t s, bool auth, const FbCallPlan& p) {
     FbWork* f = ctx->fb;
     const uint32_t n = b.n;
     // The middle kernels run over the slots in use, which only the device
@@ -2006,9 +1947,9 @@ static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest
     // HD_VAR_DEDUP 0: no table, so no message is ever marked a repeat; slots,
     // ref and every kernel are the same
     const uint32_t tw = dd_table_words(n);
-    uint32_t* dtab = ctx->var[HD_VAR_DEDUP] ? sc.dtab : nullptr;
+    uint32_t* dtab = p.dedup ? sc.dtab : nullptr;
     const uint32_t* fdict = f->fcap ? f->fdict : nullptr;
-    if (share) {
+    if (p.share) {
         // HD_VAR_PRE_SHARE 1 and no caller digests: each distinct preimage is
         // hashed once (k_pre_claim, k_pre_hash), k_fast_prep reads the rows
         const PreRows pre{sc.pre, (uint32_t*)(sc.pre + 32 * (size_t)n), (uint32_t*)(sc.pre + 36 * (size_t)n), sc.count};
@@ -2023,26 +1964,18 @@ static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest
     // HD_VAR_LEAN_INV: the inversion kernels that fit beside a capped sums;
     // a call that takes the 4-wave sums (a small batch) keeps the register
     // forms and stays out of the chain below
-    const bool lean = ctx->var[HD_VAR_LEAN_INV] && overlap;
-    if (lean) f->n_lean++;
-    if (lean) k_fast_sinv_lean<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
+    if (p.lean) k_fast_sinv_lean<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
     else k_fast_sinv<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
     // HD_VAR_SUM_CHAIN (see FbWork): behind the previous call's sums when it
     // ran on another stream; before the profile pair, so the pair times the
-    // kernel and not the wait.  Without the event (creation failed) the call
-    // runs unchained.
-    const bool chain = ctx->var[HD_VAR_SUM_CHAIN] && overlap &&
-                       (f->sums_done || hipEventCreateWithFlags(&f->sums_done, hipEventDisableTiming) == hipSuccess);
-    if (chain && f->sums_prev && f->sums_last != s && hipStreamWaitEvent(s, f->sums_done, 0) == hipSuccess) f->n_chained++;
+    // kernel and not the wait.
+    if (p.chain && f->sums.wait(s)) f->n_chained++;
     hipEvent_t* pe = fb_prof_pair(f->ev_sums, f->n_sums, f->prof);
     if (pe) (void)hipEventRecord(pe[0], s);
-    launch_sums<WP>(ctx, nb, s, n, f->gtab, f->tabs, rows, overlap);
+    launch_sums<WP>(p, nb, s, n, f->gtab, f->tabs, rows);
     if (pe) (void)hipEventRecord(pe[1], s);
-    if (chain && hipEventRecord(f->sums_done, s) == hipSuccess) {
-        f->sums_last = s;
-        f->sums_now = true;
-    }
-    if (lean) k_fast_zinv_lean<K><<<tb, 256, 0, s>>>(n, rows);
+    if (p.chain) f->sums.record(s);
+    if (p.lean) k_fast_zinv_lean<K><<<tb, 256, 0, s>>>(n, rows);
     else k_fast_zinv<K><<<tb, 256, 0, s>>>(n, rows);
     // whole blocks of 256: every wavefront's 64 messages are one bitmap word pair
     k_fast_cmp<<<nb, 256, 0, s>>>(b, rows, ctx->d_adm_perm, d_verdict, d_rec32, d_signer, sc.slow, sc.count,
@@ -2056,10 +1989,7 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
 int hd_fb_verify(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_t* d_verdict, uint8_t* d_rec32,
                  int32_t* d_signer, uint32_t* d_bitmap, hipStream_t s, bool auth) {
     FbWork* f = ctx->fb;
-    // the sums chain: what the previous call launched; this call has launched
-    // nothing yet, whichever way it returns
-    f->sums_prev = f->sums_now;
-    f->sums_now = false;
+    f->sums.begin_call();
     if (!f->done) FBCHK(hipEventCreateWithFlags(&f->done, hipEventDisableTiming), "fb event");
     const int j = f->next;
     f->next = (j + 1) % FbWork::NSCRATCH;
@@ -2120,17 +2050,21 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
         rc = hd_dev_grow(ctx, (void**)&sc.rows, &sc.cap_rows, 4 * row_words * (size_t)b.n);
         if (rc) return rc;
         const uint32_t n = b.n;
+        // the call's plan, from one snapshot of the figures earlier calls left
+        // ([2] before [3], the order k_fast_sinv's stores are written for)
+        const volatile uint32_t* est = f->est_host;
+        const FbCallPlan p = fb_plan_call(FbPlanIn{ctx->var, ctx->n_cu, n, auth, d_digest != nullptr,
+                                                   {est[0], est[1], est[2], est[3]}});
         // the repeat table, then the preimage table: one allocation, and one
         // clear over the tables this call uses
-        const bool share = ctx->var[HD_VAR_PRE_SHARE] && !d_digest;
-        if (ctx->var[HD_VAR_DEDUP] || share) {
+        if (p.dedup || p.share) {
             const size_t tab_bytes = 4 * (size_t)dd_table_words(n);
             rc = hd_dev_grow(ctx, (void**)&sc.dtab, &sc.cap_dtab, 2 * tab_bytes);
             if (rc) return rc;
-            const size_t first = ctx->var[HD_VAR_DEDUP] ? 0 : tab_bytes, last = share ? 2 * tab_bytes : tab_bytes;
+            const size_t first = p.dedup ? 0 : tab_bytes, last = p.share ? 2 * tab_bytes : tab_bytes;
             FBCHK(hipMemsetAsync((uint8_t*)sc.dtab + first, 0xFF, last - first, s), "fb table clear");
         }
-        if (share) {
+        if (p.share) {
             rc = hd_dev_grow(ctx, (void**)&sc.pre, &sc.cap_pre, 40 * (size_t)n);
             if (rc) return rc;
         }
@@ -2145,47 +2079,33 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
         rows.ref = sc.rows + 62 * (size_t)n;
         rows.cnt = sc.count;
         rows.prio = ctx->var[HD_VAR_WAVE_PRIO];
-        const int k = split_k_for(ctx, n);
-        f->last_k = k;
-        const bool overlap = !auth && sums_overlap(ctx, n);
-#define HD_SPLIT(K, WP) launch_split<K, WP>(ctx, b, d_digest, d_verdict, d_rec32, d_signer, d_bitmap, rows, sc, s, auth, share, overlap)
-        if (f->wp == HD_FB_WX) {
-            if (k == 16) HD_SPLIT(16, HD_FB_WX);
-            else HD_SPLIT(8, HD_FB_WX);
-        } else if (f->wp == HD_FB_WW) {
-            if (k == 16) HD_SPLIT(16, HD_FB_WW);
-            else HD_SPLIT(8, HD_FB_WW);
-        } else if (f->wp == HD_FB_WN) {
-            if (k == 16) HD_SPLIT(16, HD_FB_WN);
-            else HD_SPLIT(8, HD_FB_WN);
-        } else {
-            if (k == 16) HD_SPLIT(16, HD_FB_W);
-            else HD_SPLIT(8, HD_FB_W);
-        }
-#undef HD_SPLIT
+        with_width(f->wp, [&](auto wp) {
+            with_k(p.k, [&](auto k) {
+                launch_split<decltype(k)::value, decltype(wp)::value>(ctx, b, d_digest, d_verdict, d_rec32, d_signer,
+                                                                      d_bitmap, rows, sc, s, auth, p);
+            });
+        });
+        f->last_k = p.k;
+        f->n_capped += p.capped;   // hd_ctx_overlap_stats (n_chained: where the wait is placed)
+        f->n_lean += p.lean;
         FBCHK(hipGetLastError(), "split check launch");
         // k_fast_cmp wrote the valid bitmap; the slow path sets the bits of
         // its VALID messages
-        const uint32_t full = std::min(blocks, (uint32_t)std::max(ctx->n_cu, 1) * 4u);
         // HD_VAR_SLOW_LIFT: the lift kernel first (its NO_POINT verdicts leave
         // the list), or k_verify over the whole leftover list (it lifts too).
         // A leftover list is usually under one wave per SIMD, so k_verify's
         // time is one recovery's latency whatever the list length, and the
         // separate lift only adds its own chain in series.
-        const bool lift = ctx->var[HD_VAR_SLOW_LIFT] != 0;
-        if (lift) {
-            const uint32_t lift_blocks = fallback_blocks(f->est_host[0], full);
-            k_slow_lift<<<lift_blocks, 256, 0, s>>>(b, sc.slow, sc.count, d_verdict, d_rec32, d_signer, sc.slow2,
-                                                    sc.count + 1, ctx->var[HD_VAR_WAVE_PRIO], f->est_dev, rows,
-                                                    f->gtab);
+        if (p.lift) {
+            k_slow_lift<<<p.lift_blocks, 256, 0, s>>>(b, sc.slow, sc.count, d_verdict, d_rec32, d_signer, sc.slow2,
+                                                      sc.count + 1, rows.prio, f->est_dev, rows, f->gtab);
             FBCHK(hipGetLastError(), "k_slow_lift");
         }
-        const SlowCtl ctl{lift ? sc.slow2 : sc.slow, lift ? sc.count + 1 : sc.count, f->adm_slot, f->state, f->pub,
-                          d_bitmap, lift ? f->est_dev + 1 : f->est_dev, ctx->var[HD_VAR_WAVE_PRIO],
+        const SlowCtl ctl{p.lift ? sc.slow2 : sc.slow, p.lift ? sc.count + 1 : sc.count, f->adm_slot, f->state, f->pub,
+                          d_bitmap, p.lift ? f->est_dev + 1 : f->est_dev, rows.prio,
                           f->fcap ? f->fdict : nullptr, f->fnext, f->fbase, f->fcap, f->fpend_dev,
                           f->fcap ? f->fhit + 64 : nullptr, f->fkey, f->fpend_dev + 1};
-        rc = hd_launch_slow(ctx, b, d_digest, d_verdict, d_rec32, d_signer, nullptr, ctl,
-                            fallback_blocks(f->est_host[lift ? 1 : 0], full), s);
+        rc = hd_launch_slow(ctx, b, d_digest, d_verdict, d_rec32, d_signer, nullptr, ctl, p.slow_blocks, s);
         if (rc) return rc;
         return fb_learn(ctx, s);
     }

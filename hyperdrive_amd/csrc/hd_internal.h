@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/hd_verify.h"
+#include "hd_fastplan.h"
 #include "hd_fixedbase.h"
 #include "hd_verify_msg.h"
 
@@ -39,7 +40,7 @@ struct hd_ctx {
     int device = 0;
     int n_cu = 256;
     int verify_waves = 3;   // register budget of k_verify (waves per SIMD)
-    int var[HD_VAR__COUNT] = {3, 0, 1, 0, -1, 0, 2, 0, 0, 1, 16, 1, 1, 1, 1, 1};   // hd_ctx_set_variant (var[0] mirrors verify_waves)
+    int var[HD_VAR__COUNT];   // hd_ctx_set_variant; defaults from HD_VARIANTS (var[0] mirrors verify_waves)
     hipStream_t stream = nullptr;
     int pkfmt = HD_PUBKEY_COMPRESSED;   // id.NewSignatory's pubkey encoding (hd_ctx_set_pubkey_format)
     hd::ge* d_gtab = nullptr;
@@ -70,6 +71,9 @@ struct hd_ctx {
     // instead of for the whole device
     std::vector<std::pair<hipStream_t, hipEvent_t>> caller_ev;
     std::string last_error;
+    hd_ctx() {
+        for (const HdVarRow& r : HD_VARIANTS) var[r.key] = r.dflt;
+    }
 };
 
 // Record (after work just queued on s) that s uses this context; a no-op for

@@ -250,19 +250,10 @@ int hd_ctx_create(int device, hd_ctx** out) {
     }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->n_cu = prop.multiProcessorCount;
-    // variant defaults from the environment (hd_ctx_set_variant)
-    struct { int key; const char* env; } envs[] = {
-        {HD_VAR_VERIFY_WAVES, "HD_VERIFY_WAVES"}, {HD_VAR_SUM_WAVES, "HD_SUM_WAVES"},
-        {HD_VAR_SUM_PREFETCH, "HD_SUM_PF"},       {HD_VAR_SPLIT_K, "HD_FAST_K"},
-        {HD_VAR_KEY_WIDTH, "HD_FB_PW"},           {HD_VAR_WAVE_PRIO, "HD_WAVE_PRIO"},
-        {HD_VAR_FOREIGN_KEYS, "HD_FOREIGN_KEYS"}, {HD_VAR_SLOW_LIFT, "HD_SLOW_LIFT"},
-        {HD_VAR_DEDUP, "HD_DEDUP"},               {HD_VAR_PRE_SHARE, "HD_PRE_SHARE"},
-        {HD_VAR_SUM_CAP, "HD_SUM_CAP"},           {HD_VAR_SUM_CHAIN, "HD_SUM_CHAIN"},
-        {HD_VAR_LEAN_INV, "HD_LEAN_INV"},
-    };
-    for (auto& ev : envs)
-        if (const char* e = getenv(ev.env)) (void)hd_ctx_set_variant(ctx, ev.key, atoi(e));
-    if (getenv("HD_RECOVER_GLV_G")) (void)hd_ctx_set_variant(ctx, HD_VAR_RECOVER_G, 1);
+    // variant defaults from the environment (HD_RECOVER_GLV_G: present means 1)
+    for (const HdVarRow& r : HD_VARIANTS)
+        if (const char* e = r.env ? getenv(r.env) : nullptr)
+            (void)hd_ctx_set_variant(ctx, r.key, r.key == HD_VAR_RECOVER_G ? 1 : atoi(e));
     if (const char* f = getenv("HD_VERIFY_FASTPATH")) ctx->fastpath = atoi(f) != 0;
     // G tables (1G..2048G and lambda*(1G..2048G), affine), built once on the
     // host with the same code the device runs, then uploaded.
@@ -316,25 +307,7 @@ int hd_ctx_destroy(hd_ctx* ctx) {
 }
 
 int hd_ctx_set_variant(hd_ctx* ctx, int which, int value) {
-    if (!ctx || which < 0 || which >= HD_VAR__COUNT) return HD_EINVAL;
-    bool ok = false;
-    switch (which) {
-        case HD_VAR_VERIFY_WAVES: ok = value >= 2 && value <= 4; break;
-        case HD_VAR_SUM_WAVES: ok = value == 0 || (value >= 2 && value <= 4); break;
-        case HD_VAR_SUM_PREFETCH: ok = value == 1 || value == 2; break;
-        case HD_VAR_RECOVER_G: case HD_VAR_SLOW_LIFT: case HD_VAR_DEDUP: case HD_VAR_PRE_SHARE:
-        case HD_VAR_SUM_CAP: case HD_VAR_SUM_CHAIN: case HD_VAR_LEAN_INV:
-            ok = value == 0 || value == 1;
-            break;
-        case HD_VAR_SPLIT_K: ok = value == -1 || value == 8 || value == 16; break;
-        case HD_VAR_KEY_WIDTH:
-            ok = value == 0 || value == HD_FB_W || value == HD_FB_WW || value == HD_FB_WN || value == HD_FB_WX;
-            break;
-        case HD_VAR_WAVE_PRIO: ok = value >= 0 && value <= 3; break;
-        case HD_VAR_FOREIGN_KEYS: ok = value >= 0 && value <= 64; break;
-        default: ok = false;   // a key of a variant removed in round 5 (measured without gain)
-    }
-    if (!ok) return HD_EINVAL;
+    if (!ctx || !hd_var_accepts(which, value)) return HD_EINVAL;
     ctx->var[which] = value;
     if (which == HD_VAR_VERIFY_WAVES) ctx->verify_waves = value;
     return HD_OK;

@@ -126,6 +126,27 @@ class HostMath:
                        _p(ty), _p(h), _p(r), _p(vr), _p(val), _p(frm), _p(sg), _p(cl))
         return Batch(ty, h, r, vr, val, frm, sg), cl
 
+    PLAN_FIELDS = ("k", "waves", "sums_waves", "sums_pf", "overlap", "capped", "lean", "chain", "share", "dedup",
+                   "lift", "full", "lift_blocks", "slow_blocks")
+
+    def fb_plan(self, var, n_cu: int, n: int, auth: bool, caller_digests: bool, est) -> dict:
+        """fb_plan_call (hd_fastplan.h) for the variant vector var, by field name"""
+        var = np.ascontiguousarray(var, dtype=np.int32)
+        est = np.ascontiguousarray(est, dtype=np.uint32)
+        out = np.zeros(len(self.PLAN_FIELDS), np.uint32)
+        self.L.hdh_fb_plan(_p(var), ctypes.c_int(n_cu), ctypes.c_uint32(n), int(auth), int(caller_digests), _p(est),
+                           _p(out))
+        return dict(zip(self.PLAN_FIELDS, out.tolist()))
+
+    def variant(self, key: int, value: int):
+        """the variant table's row of key: (default, whether value is accepted, the widths
+        HD_FB_W, _WW, _WX, _WN of this build), or None for a key outside the table"""
+        dflt, ok = ctypes.c_int(), ctypes.c_int()
+        widths = (ctypes.c_int * 4)()
+        if self.L.hdh_variant(key, value, ctypes.byref(dflt), ctypes.byref(ok), widths) != 0:
+            return None
+        return dflt.value, bool(ok.value), list(widths)
+
     def pubkey_hash(self, fmt: int, x: int, y: int) -> bytes:
         out = ctypes.create_string_buffer(32)
         self.L.hdh_pubkey_hash(fmt, b32(x), b32(y), out)

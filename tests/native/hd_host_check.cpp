@@ -6,6 +6,7 @@
 #include <vector>
 #include "../../hyperdrive_amd/csrc/hd_gen.h"
 #include "../../hyperdrive_amd/csrc/hd_fixedbase.h"
+#include "../../hyperdrive_amd/csrc/hd_fastplan.h"
 #include "../../hyperdrive_amd/csrc/hd_scmont.h"
 #include "../../hyperdrive_amd/csrc/hd_keccak.h"
 #include "../../hyperdrive_amd/csrc/hd_modinv.h"
@@ -677,3 +678,26 @@ extern "C" int hdh_fdict_rebuild(const uint32_t* from_be, const uint32_t* slot, 
     return hd::fdict_rebuild(nd, where, from_be, slot, n) ? 1 : 0;
 }
 extern "C" int32_t hdh_fdict_find(const uint32_t* nd, const uint32_t* from_be) { return hd::fdict_find(nd, from_be); }
+
+// the known-key check's per-call plan (hd_fastplan.h): out[0..13] = k, waves,
+// the sums form's WAVES and PF, overlap, capped, lean, chain, share, dedup,
+// lift, full, lift_blocks, slow_blocks
+extern "C" void hdh_fb_plan(const int* var, int n_cu, uint32_t n, int auth, int caller_digests, const uint32_t* est,
+                            uint32_t* out) {
+    const FbCallPlan p = fb_plan_call(FbPlanIn{var, n_cu, n, auth != 0, caller_digests != 0,
+                                               {est[0], est[1], est[2], est[3]}});
+    const uint32_t v[14] = {(uint32_t)p.k, (uint32_t)p.waves, (uint32_t)p.sums_waves, (uint32_t)p.sums_pf, p.overlap,
+                            p.capped, p.lean, p.chain, p.share, p.dedup, p.lift, p.full, p.lift_blocks, p.slow_blocks};
+    memcpy(out, v, sizeof(v));
+}
+// the variant table's row of `key`: its default, whether hd_ctx_set_variant
+// accepts `value`, and the per-key table widths as compiled here
+// (HD_FB_W, _WW, _WX, _WN); -1 for a key outside the table
+extern "C" int hdh_variant(int key, int value, int* dflt, int* accepted, int* widths) {
+    if (key < 0 || key >= HD_VAR__COUNT || HD_VARIANTS[key].key != key) return -1;
+    *dflt = HD_VARIANTS[key].dflt;
+    *accepted = hd_var_accepts(key, value) ? 1 : 0;
+    const int w[4] = {HD_FB_W, HD_FB_WW, HD_FB_WX, HD_FB_WN};
+    memcpy(widths, w, sizeof(w));
+    return 0;
+}
