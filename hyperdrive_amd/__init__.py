@@ -6,10 +6,11 @@ The compute lives in ``_lib/libhdverify.so`` (HIP, gfx950) behind the C ABI of
 """
 from .verify import (BAD_RECID, BAD_RS, BAD_TYPE, CATCH_NAMES, INFINITY, NO_POINT, NOT_ADMITTED, NOT_AUTHENTIC,
                      SIGNATORY_MISMATCH, VALID, WHEN_NEVER, Batch, CaughtDecideResult, CaughtLogInsertResult,
-                     CaughtOrderedDecideResult, DecideLog, DecideResult, LogInsertResult, OrderedDecideResult,
+                     CaughtOrderedDecideResult, DecideLog, DecideResult, EvidenceLogInsertResult, LogInsertResult,
+                     OrderedDecideResult,
                      TallyResult, Verifier, VerifyResult, probe_valu)
 
 __all__ = ["Batch", "Verifier", "VerifyResult", "TallyResult", "DecideResult", "OrderedDecideResult", "DecideLog",
            "LogInsertResult", "CaughtDecideResult", "CaughtOrderedDecideResult", "CaughtLogInsertResult",
-           "CATCH_NAMES", "WHEN_NEVER", "probe_valu", "VALID", "BAD_RECID", "BAD_RS",
+           "EvidenceLogInsertResult", "CATCH_NAMES", "WHEN_NEVER", "probe_valu", "VALID", "BAD_RECID", "BAD_RS",
            "NO_POINT", "INFINITY", "SIGNATORY_MISMATCH", "NOT_ADMITTED", "BAD_TYPE", "NOT_AUTHENTIC"]

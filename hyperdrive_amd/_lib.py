@@ -122,6 +122,19 @@ class HdLogInfo(ctypes.Structure):
                 ("logpos", ctypes.c_void_p)]
 
 
+class HdLogRows(ctypes.Structure):
+    """include/hd_log.h hd_log_rows (hd_log_read, the two halves of hd_evidence_out)."""
+    _fields_ = [("cap", ctypes.c_uint32), ("n", ctypes.c_uint32), ("type", ctypes.c_void_p),
+                ("height", ctypes.c_void_p), ("round", ctypes.c_void_p), ("valid_round", ctypes.c_void_p),
+                ("value32", ctypes.c_void_p), ("from32", ctypes.c_void_p), ("value_ok", ctypes.c_void_p),
+                ("sig65", ctypes.c_void_p)]
+
+
+class HdEvidenceOut(ctypes.Structure):
+    """include/hd_log.h hd_evidence_out (hd_log_insert_evidence*)."""
+    _fields_ = [("offender", HdLogRows), ("against", HdLogRows)]
+
+
 class HdTallyTicket(ctypes.Structure):
     """include/hd_verify.h hd_tally_ticket (hd_tally_device_bitmap_async / hd_tally_collect)."""
     _fields_ = [("stage", ctypes.c_void_p), ("stage_cap", ctypes.c_size_t), ("dup", ctypes.c_int),
@@ -226,6 +239,19 @@ SIGNATURES = {
                                                          ctypes.c_void_p, ctypes.POINTER(HdDecideOut),
                                                          ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
                                                          ctypes.POINTER(HdCatchOut), ctypes.c_void_p]),
+    "hd_log_keep_signatures": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "hd_log_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                   ctypes.POINTER(HdLogRows)]),
+    "hd_log_insert_evidence": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.POINTER(HdDecideOut),
+                                              ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
+                                              ctypes.POINTER(HdCatchOut), ctypes.POINTER(HdEvidenceOut)]),
+    "hd_log_insert_evidence_device_bitmap": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch),
+                                                            ctypes.c_void_p, ctypes.c_void_p,
+                                                            ctypes.POINTER(HdDecideOut),
+                                                            ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
+                                                            ctypes.POINTER(HdCatchOut),
+                                                            ctypes.POINTER(HdEvidenceOut), ctypes.c_void_p]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

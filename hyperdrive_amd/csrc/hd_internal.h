@@ -110,10 +110,20 @@ struct DecideIn {
 // downloaded (out->dup and out->pclass are not read); `queued` runs once every
 // launch of the call is queued on the stream, before the stage's download and
 // the call's one synchronisation, so what it queues is complete on return.
+// With a catch list, `queued` also gets the records where k_catch_emit left
+// them on the device (the tables are clean by then; the records stay until the
+// context's next tally or decide): their count in hdr[1], record k in the
+// staged columns when k < H and at k - H of the overflow columns otherwise.
+struct DecideRecs {
+    const uint32_t* hdr;
+    const uint32_t *st_index, *st_against;
+    uint32_t H;
+    const uint32_t *ov_index, *ov_against;
+};
 struct DecideExt {
     uint8_t* d_dup;
     uint8_t* d_pclass;
-    int (*queued)(void* arg, hipStream_t s);
+    int (*queued)(void* arg, hipStream_t s, const DecideRecs* recs);   // recs: NULL without a catch list
     void* arg;
 };
 // Whole batch only; device batch, verdict bytes or valid bitmap, in.sched32 and

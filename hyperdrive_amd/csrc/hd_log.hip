@@ -35,6 +35,22 @@
 // after the decide's one synchronisation (a class the caller passes NULL for
 // is left out of the block: it is neither gathered nor downloaded); the log's length moves only after
 // every check has passed, so any error leaves the log as it was.
+//
+// A log that keeps signatures (hd_log_keep_signatures) has an eighth column of
+// 65 bytes per row.  k_log_append copies the batch's signatures into the joined
+// rows with the other fields, so from there on a signature is one more column:
+// k_log_keep compacts it, k_log_commit moves it, and every later reader finds
+// the whole message of joined position q in row q, retained or new.
+//
+//   k_log_gather    hd_log_read: one lane per asked position packs that row's
+//                   fields into one record of a device stage, which the host
+//                   downloads in one copy and spreads over the caller's columns
+//   k_log_evidence  hd_log_insert_evidence: the same packing for both messages
+//                   of every catch record, queued behind the decide's passes
+//                   (the records are read where k_catch_emit left them, their
+//                   count from the stage header); record k fills records 2k
+//                   and 2k + 1 of the evidence block, which follows the classes
+//                   in the stage and comes down with them
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -56,13 +72,22 @@ struct LogCols {
     uint8_t* value32;
     uint8_t* from32;
     uint8_t* vok;
+    uint8_t* sig;   // 65 bytes per row; NULL on a log that keeps no signatures
 };
-static const size_t kLogWidth[7] = {1, 8, 8, 8, 32, 32, 1};
+static const size_t kLogWidth[8] = {1, 8, 8, 8, 32, 32, 1, 65};
 static void** log_col(LogCols& c, int k) {
-    void** p[7] = {(void**)&c.type, (void**)&c.height, (void**)&c.round, (void**)&c.vround,
-                   (void**)&c.value32, (void**)&c.from32, (void**)&c.vok};
+    void** p[8] = {(void**)&c.type, (void**)&c.height, (void**)&c.round, (void**)&c.vround,
+                   (void**)&c.value32, (void**)&c.from32, (void**)&c.vok, (void**)&c.sig};
     return p[k];
 }
+
+// One message packed for the host (k_log_gather, k_log_evidence): 8-byte fields
+// first, so a record at a multiple of 8 bytes is written with aligned stores.
+enum : uint32_t {
+    ROW_HEIGHT = 0, ROW_ROUND = 8, ROW_VROUND = 16, ROW_VALUE = 24, ROW_FROM = 56, ROW_TYPE = 88, ROW_VOK = 89,
+    ROW_SIG = 90, ROW_BYTES = 96, ROW_BYTES_SIG = 160
+};
+static_assert(ROW_SIG + 65 <= ROW_BYTES_SIG && ROW_BYTES % 8 == 0 && ROW_BYTES_SIG % 8 == 0, "packed row");
 
 struct hd_log {
     hd_ctx* ctx = nullptr;
@@ -82,6 +107,10 @@ struct hd_log {
     DevBuf in_vok;                // the host form's uploaded value_ok
     char* host = nullptr;         // pinned image of res
     size_t host_cap = 0;
+    bool keep_sig = false;        // hd_log_keep_signatures
+    uint32_t guess_ev = 256;      // records of evidence staged with the classes; more take a second copy
+    DevBuf pos;                   // hd_log_read: the asked positions
+    hipStream_t commit_stream = nullptr;   // the caller's stream the last k_log_commit went on, if it was one
 };
 
 __device__ __forceinline__ void copy_row(const LogCols& dst, size_t j, const uint8_t* type, const int64_t* height,
@@ -102,6 +131,20 @@ __device__ __forceinline__ void copy_row(const LogCols& dst, size_t j, const uin
     df[1] = f1;
 }
 
+// 65·i is no multiple of 4 and a device batch's base may be misaligned too, hence bytes.  All 65 loads are
+// issued before the first store, so a row costs one trip to memory, not 65 in turn (round 14: a plain
+// load-store loop cost an insert of 8,000 that keeps 5,000 some 40 µs).
+__device__ __forceinline__ void load_sig(uint8_t (&r)[65], const uint8_t* __restrict__ src) {
+#pragma unroll
+    for (int t = 0; t < 65; t++) r[t] = src[t];
+}
+__device__ __forceinline__ void copy_sig(uint8_t* __restrict__ dst, size_t j, const uint8_t* __restrict__ src, size_t i) {
+    uint8_t r[65];
+    load_sig(r, src + 65 * i);
+#pragma unroll
+    for (int t = 0; t < 65; t++) dst[65 * j + t] = r[t];
+}
+
 __global__ __launch_bounds__(256) void k_log_append(DevBatch b, const uint8_t* __restrict__ verdict,
                                                     const uint32_t* __restrict__ bitmap,
                                                     const uint8_t* __restrict__ value_ok, int64_t height, uint32_t L,
@@ -115,6 +158,7 @@ __global__ __launch_bounds__(256) void k_log_append(DevBatch b, const uint8_t* _
         const uint32_t i = q - L;
         copy_row(lg, q, b.type, b.height, b.round, b.valid_round, b.value32, b.from32, i);
         lg.vok[q] = value_ok ? (value_ok[i] ? 1 : 0) : 1;
+        if (lg.sig) copy_sig(lg.sig, q, b.sig65, i);
         bool ok = b.height[i] == height;
         if (verdict && verdict[i] != V_VALID) ok = false;
         if (bitmap && !((bitmap[i >> 5] >> (i & 31)) & 1u)) ok = false;
@@ -184,6 +228,7 @@ __global__ __launch_bounds__(256) void k_log_keep(uint32_t total, uint32_t L, co
     if (keep) {   // j < the batch's size: tmp has a row for every new message
         copy_row(tmp, j, lg.type, lg.height, lg.round, lg.vround, lg.value32, lg.from32, q);
         tmp.vok[j] = lg.vok[q];
+        if (tmp.sig) copy_sig(tmp.sig, j, lg.sig, q);
     }
 }
 
@@ -193,6 +238,55 @@ __global__ __launch_bounds__(256) void k_log_commit(uint32_t kept, uint32_t L, L
     for (uint32_t j = blockIdx.x * blockDim.x + threadIdx.x; j < kept; j += stride) {
         copy_row(lg, (size_t)L + j, tmp.type, tmp.height, tmp.round, tmp.vround, tmp.value32, tmp.from32, j);
         lg.vok[(size_t)L + j] = tmp.vok[j];
+        if (lg.sig) copy_sig(lg.sig, (size_t)L + j, tmp.sig, j);
+    }
+}
+
+// row q of the columns as one packed record at dst (8-byte aligned)
+__device__ __forceinline__ void pack_row(uint8_t* dst, const LogCols& lg, size_t q, bool sig) {
+    int64_t* d = reinterpret_cast<int64_t*>(dst);
+    d[ROW_HEIGHT / 8] = lg.height[q];
+    d[ROW_ROUND / 8] = lg.round[q];
+    d[ROW_VROUND / 8] = lg.vround[q];
+    const uint2* v = reinterpret_cast<const uint2*>(lg.value32 + 32 * q);
+    const uint2* f = reinterpret_cast<const uint2*>(lg.from32 + 32 * q);
+    uint2* dv = reinterpret_cast<uint2*>(dst + ROW_VALUE);
+    uint2* df = reinterpret_cast<uint2*>(dst + ROW_FROM);
+    for (int k = 0; k < 4; k++) {
+        dv[k] = v[k];
+        df[k] = f[k];
+    }
+    dst[ROW_TYPE] = lg.type[q];
+    dst[ROW_VOK] = lg.vok[q];
+    if (sig) copy_sig(dst + ROW_SIG, 0, lg.sig, q);
+}
+
+// hd_log_read: record k is entry pos[k], or first + k without a list (the host has checked every position)
+__global__ __launch_bounds__(256) void k_log_gather(const uint32_t* __restrict__ pos, uint32_t first, uint32_t n,
+                                                    LogCols lg, uint8_t* __restrict__ rows, uint32_t row_bytes) {
+    const uint32_t stride = gridDim.x * blockDim.x;
+    for (uint32_t k = blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride)
+        pack_row(rows + (size_t)row_bytes * k, lg, pos ? pos[k] : first + k, row_bytes == ROW_BYTES_SIG);
+}
+
+// One lane per message of a catch record: lane 2k packs record k's offender, lane 2k + 1 the message it
+// contradicts, both from the joined rows (a retained entry below L, this batch's messages from L on).  A
+// position that is no joined row -- HD_WHEN_NEVER, the against of an out-of-turn propose -- gives zero bytes.
+// `room` records fit in rows.
+__global__ __launch_bounds__(256) void k_log_evidence(DecideRecs r, uint32_t room, uint32_t total, LogCols lg,
+                                                      uint8_t* __restrict__ rows, uint32_t row_bytes) {
+    const uint32_t recs = min(r.hdr[1], room), stride = gridDim.x * blockDim.x;
+    for (uint32_t t = blockIdx.x * blockDim.x + threadIdx.x; t < 2 * recs; t += stride) {
+        const uint32_t k = t >> 1;
+        const uint32_t* col = (t & 1u) ? (k < r.H ? r.st_against : r.ov_against) : (k < r.H ? r.st_index : r.ov_index);
+        const uint32_t q = col[k < r.H ? k : k - r.H];
+        uint8_t* dst = rows + (size_t)row_bytes * t;
+        if (q < total) {
+            pack_row(dst, lg, q, row_bytes == ROW_BYTES_SIG);
+        } else {
+            uint2* z = reinterpret_cast<uint2*>(dst);
+            for (uint32_t w = 0; w < row_bytes / 8; w++) z[w] = make_uint2(0u, 0u);
+        }
     }
 }
 
@@ -204,19 +298,20 @@ __global__ __launch_bounds__(256) void k_log_commit(uint32_t kept, uint32_t L, L
     } while (0)
 
 static void cols_free(LogCols& c) {
-    for (int k = 0; k < 7; k++) {
+    for (int k = 0; k < 8; k++) {
         void** p = log_col(c, k);
         if (*p) (void)hipFree(*p);
         *p = nullptr;
     }
 }
 
-// rows for `need` items; the first `keep` rows survive a regrow (copied on s)
-static int cols_grow(hd_ctx* ctx, LogCols& c, size_t& cap, size_t need, size_t keep, hipStream_t s) {
+// rows for `need` items; the first `keep` rows survive a regrow (copied on s).  ncols: 8 on a log that keeps
+// signatures, 7 otherwise (the setting changes only while the log holds no columns)
+static int cols_grow(hd_ctx* ctx, LogCols& c, size_t& cap, size_t need, size_t keep, hipStream_t s, int ncols) {
     if (need <= cap) return HD_OK;
     const size_t want = std::max(need + need / 4, (size_t)4096);
     LogCols nw{};
-    for (int k = 0; k < 7; k++) {
+    for (int k = 0; k < ncols; k++) {
         hipError_t e = hipMalloc(log_col(nw, k), kLogWidth[k] * want);
         if (e != hipSuccess) {
             cols_free(nw);
@@ -225,7 +320,7 @@ static int cols_grow(hd_ctx* ctx, LogCols& c, size_t& cap, size_t need, size_t k
     }
     if (keep) {
         hipError_t e = hipSuccess;
-        for (int k = 0; k < 7 && e == hipSuccess; k++)
+        for (int k = 0; k < ncols && e == hipSuccess; k++)
             e = hipMemcpyAsync(*log_col(nw, k), *log_col(c, k), kLogWidth[k] * keep, hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) {
@@ -243,14 +338,47 @@ static int buf_grow(hd_ctx* ctx, DevBuf& b, size_t need) { return hd_dev_grow(ct
 
 static size_t log_pad(size_t n) { return (n + 63) & ~(size_t)63; }
 
+static int host_grow(hd_log* lg, size_t need) {
+    hd_ctx* ctx = lg->ctx;
+    if (lg->host_cap >= need) return HD_OK;
+    if (lg->host) (void)hipHostFree(lg->host);
+    lg->host = nullptr;
+    lg->host_cap = 0;
+    LCHK(hipHostMalloc((void**)&lg->host, need + (need >> 2), hipHostMallocDefault), "log host stage");
+    lg->host_cap = need + (need >> 2);
+    return HD_OK;
+}
+
+static bool rows_ok(const hd_log_rows* r) {
+    return r && (r->cap == 0 || (r->type && r->height && r->round && r->valid_round && r->value32 && r->from32 &&
+                                 r->value_ok));
+}
+
+// packed record -> row k of the caller's columns
+static void unpack_row(const char* src, hd_log_rows* o, size_t k) {
+    memcpy(o->height + k, src + ROW_HEIGHT, 8);
+    memcpy(o->round + k, src + ROW_ROUND, 8);
+    memcpy(o->valid_round + k, src + ROW_VROUND, 8);
+    memcpy(o->value32 + 32 * k, src + ROW_VALUE, 32);
+    memcpy(o->from32 + 32 * k, src + ROW_FROM, 32);
+    o->type[k] = (uint8_t)src[ROW_TYPE];
+    o->value_ok[k] = (uint8_t)src[ROW_VOK];
+    if (o->sig65) memcpy(o->sig65 + 65 * k, src + ROW_SIG, 65);
+}
+
 struct KeepArgs {
     hd_log* lg;
     uint32_t n, total, nb;
     size_t dup_off, pc_off, res_bytes;   // dup_off / pc_off: 0 when the caller does not take the class
+    // evidence: its block starts at ev_off of res with room for n records (two packed rows of ev_row bytes
+    // each), of which the first ev_staged come down with the classes
+    bool ev;
+    size_t ev_off;
+    uint32_t ev_row, ev_staged;
 };
 
 // hd_decide_run's hook: dup / pclass are complete on the stream
-static int log_queue_keep(void* arg, hipStream_t s) {
+static int log_queue_keep(void* arg, hipStream_t s, const DecideRecs* recs) {
     const KeepArgs* a = static_cast<const KeepArgs*>(arg);
     hd_log* lg = a->lg;
     hd_ctx* ctx = lg->ctx;
@@ -263,7 +391,14 @@ static int log_queue_keep(void* arg, hipStream_t s) {
                                      (uint32_t*)(res + lp_off), a->dup_off ? (uint8_t*)(res + a->dup_off) : nullptr,
                                      a->pc_off ? (uint8_t*)(res + a->pc_off) : nullptr);
     LCHK(hipGetLastError(), "log keep kernels");
-    LCHK(hipMemcpyAsync(lg->host, res, a->res_bytes, hipMemcpyDeviceToHost, s), "log download");
+    size_t down = a->res_bytes;
+    if (a->ev && recs && a->n) {   // only a message of this batch is an offender: at most n records
+        const uint32_t grid = std::min<uint32_t>((2u * a->n + 255u) / 256u, (uint32_t)ctx->n_cu * 16u);
+        k_log_evidence<<<grid, 256, 0, s>>>(*recs, a->n, a->total, lg->lg, (uint8_t*)(res + a->ev_off), a->ev_row);
+        LCHK(hipGetLastError(), "log evidence");
+        down = a->ev_off + 2 * (size_t)a->ev_row * a->ev_staged;
+    }
+    LCHK(hipMemcpyAsync(lg->host, res, down, hipMemcpyDeviceToHost, s), "log download");
     return HD_OK;
 }
 
@@ -276,13 +411,14 @@ static bool log_out_ok(const hd_decide_out* o, const hd_decide_order* w) {
 // db, d_verdict / d_bitmap (one of them) and d_vok are device pointers
 static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, const uint32_t* d_bitmap,
                       const uint8_t* d_vok, hd_decide_out* out, hd_decide_order* order, hd_log_info* info,
-                      hd_catch_out* caught, hipStream_t s) {
+                      hd_catch_out* caught, hd_evidence_out* ev, hipStream_t s) {
     hd_ctx* ctx = lg->ctx;
     const uint32_t n = db->n, L = lg->L, total = L + n;
     if (total == 0) return HD_OK;
     const uint32_t nb = (total + 255u) / 256u;
-    int rc = cols_grow(ctx, lg->lg, lg->cap_items, total, L, s);
-    if (!rc) rc = cols_grow(ctx, lg->tmp, lg->cap_new, std::max(n, 1u), 0, s);
+    const int ncols = lg->keep_sig ? 8 : 7;
+    int rc = cols_grow(ctx, lg->lg, lg->cap_items, total, L, s, ncols);
+    if (!rc) rc = cols_grow(ctx, lg->tmp, lg->cap_new, std::max(n, 1u), 0, s, ncols);
     if (!rc) rc = buf_grow(ctx, lg->vd, total);
     if (!rc) rc = buf_grow(ctx, lg->dup, total);
     if (!rc) rc = buf_grow(ctx, lg->pclass, total);
@@ -292,16 +428,14 @@ static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, 
     const size_t cls_off = 64 + log_pad(4 * (size_t)n);
     const size_t dup_off = out->dup ? cls_off : 0, pc_off = out->pclass ? cls_off + (out->dup ? log_pad(n) : 0) : 0;
     const size_t res_bytes = cls_off + (out->dup ? log_pad(n) : 0) + (out->pclass ? log_pad(n) : 0);
-    if (!rc) rc = buf_grow(ctx, lg->res, res_bytes);
+    // the evidence block behind them: room for n records on the device, the first ev_staged in the download
+    const size_t ev_off = log_pad(res_bytes);
+    const uint32_t ev_row = lg->keep_sig ? ROW_BYTES_SIG : ROW_BYTES, ev_staged = ev ? std::min(lg->guess_ev, n) : 0u;
+    if (!rc) rc = buf_grow(ctx, lg->res, ev ? ev_off + 2 * (size_t)ev_row * n : res_bytes);
+    if (!rc) rc = host_grow(lg, ev ? ev_off + 2 * (size_t)ev_row * ev_staged : res_bytes);
     if (rc) return rc;
-    if (lg->host_cap < res_bytes) {
-        if (lg->host) (void)hipHostFree(lg->host);
-        lg->host = nullptr;
-        lg->host_cap = 0;
-        LCHK(hipHostMalloc((void**)&lg->host, res_bytes + (res_bytes >> 2), hipHostMallocDefault), "log host stage");
-        lg->host_cap = res_bytes + (res_bytes >> 2);
-    }
-    DevBatch b{n, db->type, db->height, db->round, db->valid_round, db->value32, db->from32, nullptr};
+    DevBatch b{n, db->type, db->height, db->round, db->valid_round, db->value32, db->from32,
+               lg->keep_sig ? db->sig65 : nullptr};
     const uint32_t grid = std::min<uint32_t>(nb, (uint32_t)ctx->n_cu * 16u);
     k_log_append<<<grid, 256, 0, s>>>(b, d_verdict, d_bitmap, d_vok, lg->height, L, lg->lg, (uint8_t*)lg->vd.p);
     LCHK(hipGetLastError(), "log append");
@@ -314,12 +448,13 @@ static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, 
     jb.value32 = lg->lg.value32;
     jb.from32 = lg->lg.from32;
     jb.sig65 = nullptr;
-    KeepArgs ka{lg, n, total, nb, dup_off, pc_off, res_bytes};
+    KeepArgs ka{lg, n, total, nb, dup_off, pc_off, res_bytes, ev != nullptr, ev_off, ev_row, ev_staged};
     const DecideExt ext{(uint8_t*)lg->dup.p, (uint8_t*)lg->pclass.p, log_queue_keep, &ka};
     rc = hd_decide_run(ctx, &jb, (const uint8_t*)lg->vd.p, nullptr,
                        DecideIn{lg->f, lg->n_sched, lg->n_sched ? lg->d_sched : nullptr, lg->lg.vok}, out, s, order,
                        &ext, caught);
     (void)hd_ctx_note_stream(ctx, s);
+    if (ev) lg->guess_ev = std::max<uint32_t>(256u, caught->n + caught->n / 4);   // also after HD_ECAP: the retry is staged
     if (rc) return rc;
     // the items are the joined coordinates, so the records are final; they are in ascending index and a
     // retained entry, the only message of its key, is never an offender
@@ -340,31 +475,62 @@ static int log_insert(hd_log* lg, const hd_batch* db, const uint8_t* d_verdict, 
     if (info->logpos) memcpy(info->logpos, lg->host + lp_off, 4 * (size_t)n);
     if (out->dup) memcpy(out->dup, lg->host + dup_off, n);
     if (out->pclass) memcpy(out->pclass, lg->host + pc_off, n);
+    if (ev) {   // caught->n <= caught->cap <= both row sets' cap, and <= n by the check above
+        const uint32_t recs = caught->n, staged = std::min(recs, ev_staged);
+        const auto spread = [&](const char* src, uint32_t k0, uint32_t cnt) {
+            for (uint32_t k = 0; k < cnt; k++) {
+                unpack_row(src + 2 * (size_t)ev_row * k, &ev->offender, k0 + k);
+                unpack_row(src + 2 * (size_t)ev_row * k + ev_row, &ev->against, k0 + k);
+            }
+        };
+        spread(lg->host + ev_off, 0, staged);
+        if (recs > staged) {   // past the staged records: a second copy, as the catch list's own overflow
+            const size_t more = 2 * (size_t)ev_row * (recs - staged);
+            rc = host_grow(lg, more);   // everything the stage held has been copied out by now
+            if (rc) return rc;
+            char* dst = lg->host;
+            LCHK(hipMemcpyAsync(dst, (char*)lg->res.p + ev_off + 2 * (size_t)ev_row * staged, more,
+                                hipMemcpyDeviceToHost, s),
+                 "log evidence overflow");
+            LCHK(hipStreamSynchronize(s), "log evidence overflow sync");
+            spread(dst, staged, recs - staged);
+        }
+        ev->offender.n = ev->against.n = recs;
+    }
     if (kept) {   // the kept rows behind the retained ones; ordered before the next call by the stream
         k_log_commit<<<std::min<uint32_t>((kept + 255u) / 256u, (uint32_t)ctx->n_cu * 16u), 256, 0, s>>>(
             kept, L, lg->tmp, lg->lg);
         LCHK(hipGetLastError(), "log commit");
         (void)hd_ctx_note_stream(ctx, s);
+        lg->commit_stream = s != ctx->stream ? s : nullptr;   // hd_log_read gathers on the context's stream
     }
     lg->L = L + kept;
     return HD_OK;
 }
 
 static bool log_args_ok(const hd_log* lg, const hd_batch* b, const hd_decide_out* out, const hd_decide_order* order,
-                        hd_log_info* info, const hd_catch_out* caught) {
+                        hd_log_info* info, const hd_catch_out* caught, const hd_evidence_out* ev) {
     if (!lg || !lg->ctx || !b || !info || !log_out_ok(out, order)) return false;
     if (caught && caught->cap && (!caught->index || !caught->against || !caught->kind)) return false;
     if (b->n && (!b->type || !b->height || !b->round || !b->value32 || !b->from32)) return false;
+    if (b->n && lg->keep_sig && !b->sig65) return false;
+    if (ev) {   // rows for every record the list has room for, so the list's is the only capacity error
+        if (!caught || !rows_ok(&ev->offender) || !rows_ok(&ev->against)) return false;
+        if (ev->offender.cap < caught->cap || ev->against.cap < caught->cap) return false;
+        if (!lg->keep_sig && (ev->offender.sig65 || ev->against.sig65)) return false;
+    }
     return (uint64_t)lg->L + b->n < (1ull << 30);
 }
 
 // hd_log_insert and hd_log_insert_catch (caught non-NULL, checked by the caller)
 static int insert_host(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
-                       hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught) {
-    if (!log_args_ok(lg, batch, out, order, info, caught) || (batch->n && !verdict)) return HD_EINVAL;
+                       hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught,
+                       hd_evidence_out* ev) {
+    if (!log_args_ok(lg, batch, out, order, info, caught, ev) || (batch->n && !verdict)) return HD_EINVAL;
     hd_ctx* ctx = lg->ctx;
     out->n = 0;
     if (caught) caught->n = 0;
+    if (ev) ev->offender.n = ev->against.n = 0;
     info->base = lg->L;
     info->kept = info->relogged = 0;
     const uint32_t n = batch->n;
@@ -374,7 +540,7 @@ static int insert_host(hd_log* lg, const hd_batch* batch, const uint8_t* verdict
     const uint8_t *d_v = nullptr, *d_vok = nullptr;
     if (n) {
         hd_batch hb = *batch;
-        hb.sig65 = nullptr;   // not kept: Equal ignores it
+        if (!lg->keep_sig) hb.sig65 = nullptr;   // not kept: Equal ignores it
         int rc = hd_upload_batch(ctx, &hb, &db);
         if (!rc) rc = hd_dev_grow(ctx, &ctx->bufs[BUF_VERDICT].p, &ctx->bufs[BUF_VERDICT].cap, n);
         if (!rc && value_ok) rc = buf_grow(ctx, lg->in_vok, n);
@@ -387,21 +553,22 @@ static int insert_host(hd_log* lg, const hd_batch* batch, const uint8_t* verdict
             d_vok = (const uint8_t*)lg->in_vok.p;
         }
     }
-    return log_insert(lg, &db, d_v, nullptr, d_vok, out, order, info, caught, ctx->stream);
+    return log_insert(lg, &db, d_v, nullptr, d_vok, out, order, info, caught, ev, ctx->stream);
 }
 
 static int insert_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap, const uint8_t* d_value_ok,
                          hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught,
-                         void* stream) {
-    if (!log_args_ok(lg, dbatch, out, order, info, caught) || (dbatch->n && !d_valid_bitmap)) return HD_EINVAL;
+                         hd_evidence_out* ev, void* stream) {
+    if (!log_args_ok(lg, dbatch, out, order, info, caught, ev) || (dbatch->n && !d_valid_bitmap)) return HD_EINVAL;
     hd_ctx* ctx = lg->ctx;
     out->n = 0;
     if (caught) caught->n = 0;
+    if (ev) ev->offender.n = ev->against.n = 0;
     info->base = lg->L;
     info->kept = info->relogged = 0;
     (void)hipSetDevice(ctx->device);
     return log_insert(lg, dbatch, nullptr, dbatch->n ? d_valid_bitmap : nullptr, d_value_ok, out, order, info, caught,
-                      stream ? (hipStream_t)stream : ctx->stream);
+                      ev, stream ? (hipStream_t)stream : ctx->stream);
 }
 
 extern "C" {
@@ -422,7 +589,7 @@ int hd_log_destroy(hd_log* lg) {
     (void)hipDeviceSynchronize();   // a commit's copies may still be queued on a caller's stream
     cols_free(lg->lg);
     cols_free(lg->tmp);
-    DevBuf* bufs[] = {&lg->vd, &lg->dup, &lg->pclass, &lg->blk, &lg->res, &lg->in_vok};
+    DevBuf* bufs[] = {&lg->vd, &lg->dup, &lg->pclass, &lg->blk, &lg->res, &lg->in_vok, &lg->pos};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     if (lg->d_sched) (void)hipFree(lg->d_sched);
@@ -460,26 +627,92 @@ int hd_log_len(const hd_log* lg, int64_t* height, uint32_t* entries) {
 
 int hd_log_insert(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
                   hd_decide_out* out, hd_decide_order* order, hd_log_info* info) {
-    return insert_host(lg, batch, verdict, value_ok, out, order, info, nullptr);
+    return insert_host(lg, batch, verdict, value_ok, out, order, info, nullptr, nullptr);
 }
 
 int hd_log_insert_device_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
                                 const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
                                 hd_log_info* info, void* stream) {
-    return insert_bitmap(lg, dbatch, d_valid_bitmap, d_value_ok, out, order, info, nullptr, stream);
+    return insert_bitmap(lg, dbatch, d_valid_bitmap, d_value_ok, out, order, info, nullptr, nullptr, stream);
 }
 
 int hd_log_insert_catch(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
                         hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught) {
     if (!caught) return HD_EINVAL;
-    return insert_host(lg, batch, verdict, value_ok, out, order, info, caught);
+    return insert_host(lg, batch, verdict, value_ok, out, order, info, caught, nullptr);
 }
 
 int hd_log_insert_catch_device_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
                                       const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
                                       hd_log_info* info, hd_catch_out* caught, void* stream) {
     if (!caught) return HD_EINVAL;
-    return insert_bitmap(lg, dbatch, d_valid_bitmap, d_value_ok, out, order, info, caught, stream);
+    return insert_bitmap(lg, dbatch, d_valid_bitmap, d_value_ok, out, order, info, caught, nullptr, stream);
+}
+
+int hd_log_insert_evidence(hd_log* lg, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
+                           hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught,
+                           hd_evidence_out* evidence) {
+    if (!caught || !evidence) return HD_EINVAL;
+    return insert_host(lg, batch, verdict, value_ok, out, order, info, caught, evidence);
+}
+
+int hd_log_insert_evidence_device_bitmap(hd_log* lg, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                         const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
+                                         hd_log_info* info, hd_catch_out* caught, hd_evidence_out* evidence,
+                                         void* stream) {
+    if (!caught || !evidence) return HD_EINVAL;
+    return insert_bitmap(lg, dbatch, d_valid_bitmap, d_value_ok, out, order, info, caught, evidence, stream);
+}
+
+int hd_log_keep_signatures(hd_log* lg, int on) {
+    if (!lg || lg->L != 0) return HD_EINVAL;
+    if (lg->keep_sig == (on != 0)) return HD_OK;
+    // the columns of an earlier height have the other shape: the next insert allocates them again
+    (void)hipSetDevice(lg->device);
+    (void)hipDeviceSynchronize();   // a commit may still be queued on a caller's stream
+    cols_free(lg->lg);
+    cols_free(lg->tmp);
+    lg->cap_items = lg->cap_new = 0;
+    lg->keep_sig = on != 0;
+    return HD_OK;
+}
+
+int hd_log_read(hd_log* lg, const uint32_t* pos, uint32_t first, uint32_t n, hd_log_rows* out) {
+    if (!lg || !lg->ctx || !rows_ok(out)) return HD_EINVAL;
+    out->n = 0;
+    if (out->cap < n || (out->sig65 && !lg->keep_sig)) return HD_EINVAL;
+    if (pos) {
+        for (uint32_t k = 0; k < n; k++)
+            if (pos[k] >= lg->L) return HD_EINVAL;
+    } else if ((uint64_t)first + n > lg->L) {
+        return HD_EINVAL;
+    }
+    if (n == 0) return HD_OK;
+    hd_ctx* ctx = lg->ctx;
+    hipStream_t s = ctx->stream;
+    (void)hipSetDevice(ctx->device);
+    const uint32_t row = out->sig65 ? ROW_BYTES_SIG : ROW_BYTES;
+    const size_t bytes = (size_t)row * n;
+    int rc = buf_grow(ctx, lg->res, bytes);
+    if (!rc) rc = host_grow(lg, bytes);
+    if (!rc && pos) rc = buf_grow(ctx, lg->pos, 4 * (size_t)n);
+    if (rc) return rc;
+    if (lg->commit_stream) {
+        // the last insert's commit ran on a caller's stream: wait for the event hd_ctx_note_stream recorded
+        // behind it (a stream that is no longer listed has completed that work)
+        for (const auto& se : ctx->caller_ev)
+            if (se.first == lg->commit_stream) LCHK(hipStreamWaitEvent(s, se.second, 0), "log read wait");
+        lg->commit_stream = nullptr;
+    }
+    if (pos) LCHK(hipMemcpyAsync(lg->pos.p, pos, 4 * (size_t)n, hipMemcpyHostToDevice, s), "log read positions");
+    k_log_gather<<<std::min<uint32_t>((n + 255u) / 256u, (uint32_t)ctx->n_cu * 16u), 256, 0, s>>>(
+        pos ? (const uint32_t*)lg->pos.p : nullptr, first, n, lg->lg, (uint8_t*)lg->res.p, row);
+    LCHK(hipGetLastError(), "log gather");
+    LCHK(hipMemcpyAsync(lg->host, lg->res.p, bytes, hipMemcpyDeviceToHost, s), "log read download");
+    LCHK(hipStreamSynchronize(s), "log read sync");
+    for (uint32_t k = 0; k < n; k++) unpack_row(lg->host + (size_t)row * k, out, k);
+    out->n = n;
+    return HD_OK;
 }
 
 }  // extern "C"

@@ -2365,8 +2365,10 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
                                             (uint32_t*)(st + when_off), (uint32_t*)(st + until_off),
                                             (uint32_t*)(ovf + ovw_off), (uint32_t*)(ovf + ovu_off));
     }
+    DecideRecs recs_dev{};
     if (caught) {   // likewise; Bc, pre_c and the C totals are free after the firsts pass
         const CatchCols cs = catch_cols(st + catch_off, Hc), co = catch_cols(covf, m);
+        recs_dev = DecideRecs{(const uint32_t*)st, cs.index, cs.against, Hc, co.index, co.against};
         with_ipb(p.ipb, [&](auto ipb) {
             constexpr uint32_t IPB = decltype(ipb)::value;
             k_catch_flags<IPB><<<p.nbo, 256, 0, s>>>(m, d_dup, d_pclass, p.Bc, p.pre_c, p.blk + p.nbo);
@@ -2378,7 +2380,7 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
     TCHK(hipGetLastError(), "decide order kernels");
     tally_plan_done(ctx, p);
     if (ext && ext->queued) {
-        rc = ext->queued(ext->arg, s);
+        rc = ext->queued(ext->arg, s, caught ? &recs_dev : nullptr);
         if (rc) return rc;
     }
     const char* hs = tally_download(ctx, st, total, s, &rc);

@@ -229,17 +229,18 @@ class Ingress:
         self._clean = (self.height, mq.inserts)
         return FlushResult(b, senders, status, double_of, None, mq.last_removed, events)
 
-    def open_log(self, schedule=None):
+    def open_log(self, schedule=None, keep_signatures=False):
         """Open a DecideLog (hd_log) at the ingress's height and f: the propose
         log and every quorum rule of the height, kept on the device from flush
         to flush.  schedule: the round-robin order for the turn check (None:
-        no turn check).  Returns the log (also ``self.log``)."""
+        no turn check).  keep_signatures: the log keeps whole messages
+        (Verifier.open_log).  Returns the log (also ``self.log``)."""
         if self.log is not None:
             self.log.close()
-        self.log = self.v.open_log(self.height, self.f or 0, schedule)
+        self.log = self.v.open_log(self.height, self.f or 0, schedule, keep_signatures=keep_signatures)
         return self.log
 
-    def flush_decide(self, value_ok=None, catch=False):
+    def flush_decide(self, value_ok=None, catch=False, evidence=False):
         """flush() followed by one insert of the consumed batch into the open
         log.  Every consumed message is authenticated and admitted, so its
         verdict is VALID.  value_ok stands in for validator.Valid on the
@@ -247,14 +248,16 @@ class Ingress:
         consumed message, or -- the consumed batch is not known before the
         flush -- a callable that takes the consumed Batch and returns those
         bytes.  catch: the insert also returns the catch list of the consumed
-        messages (DecideLog.insert's ``catch``: ``dec.caught``).  Returns
-        (FlushResult, LogInsertResult)."""
+        messages (DecideLog.insert's ``catch``: ``dec.caught``); evidence (with
+        catch): and both whole messages of every record, the consumed batch's
+        signatures included (``dec.evidence_offender`` / ``dec.evidence_against``).
+        Returns (FlushResult, LogInsertResult)."""
         if self.log is None:
             raise RuntimeError("flush_decide without open_log")
         res = self.flush()
         b = res.consumed
         vok = value_ok(b) if callable(value_ok) else value_ok
-        return res, self.log.insert(b, np.zeros(len(b), np.uint8), vok, catch=catch)
+        return res, self.log.insert(b, np.zeros(len(b), np.uint8), vok, catch=catch, evidence=evidence)
 
     def advance_height(self, height: int) -> None:
         """The Process's own height change after a commit (process.go:710-725:

@@ -297,6 +297,39 @@ class CaughtLogInsertResult(LogInsertResult, _Caught):
     caught_kind: np.ndarray = None
 
 
+@dataclass
+class EvidenceLogInsertResult(CaughtLogInsertResult):
+    """A CaughtLogInsertResult with the whole messages of every record
+    (hd_evidence_out): row k of ``evidence_offender`` and row k of
+    ``evidence_against`` are the two messages of ``caught[k]``, as the
+    reference's Catcher takes them.  The against row of an out-of-turn propose
+    is all zero bytes.  On a log that keeps no signatures both ``sig`` arrays
+    are zero."""
+    evidence_offender: Batch = None
+    evidence_against: Batch = None
+    evidence_offender_value_ok: np.ndarray = None   # uint8[records]
+    evidence_against_value_ok: np.ndarray = None
+
+
+def _rows_struct(n: int, sig: bool):
+    """An hd_log_rows with room for n rows, and its arrays."""
+    from ._lib import HdLogRows
+    m = max(n, 1)
+    a = {"type": np.zeros(m, np.uint8), "height": np.zeros(m, np.int64), "round": np.zeros(m, np.int64),
+         "valid_round": np.zeros(m, np.int64), "value32": np.zeros((m, 32), np.uint8),
+         "from32": np.zeros((m, 32), np.uint8), "value_ok": np.zeros(m, np.uint8), "sig65": np.zeros((m, 65), np.uint8)}
+    r = HdLogRows(n, 0, _ptr(a["type"]), _ptr(a["height"]), _ptr(a["round"]), _ptr(a["valid_round"]),
+                  _ptr(a["value32"]), _ptr(a["from32"]), _ptr(a["value_ok"]), _ptr(a["sig65"]) if sig else None)
+    return r, a
+
+
+def _rows_batch(n: int, a) -> Tuple[Batch, np.ndarray]:
+    """The first n rows of _rows_struct's arrays as (Batch, value_ok)."""
+    return (Batch._wrap(a["type"][:n].copy(), a["height"][:n].copy(), a["round"][:n].copy(),
+                        a["valid_round"][:n].copy(), a["value32"][:n].copy(), a["from32"][:n].copy(),
+                        a["sig65"][:n].copy()), a["value_ok"][:n].copy())
+
+
 def _catch_struct(n: int):
     """An hd_catch_out with room for every message of a batch of n."""
     from ._lib import HdCatchOut
@@ -315,7 +348,8 @@ class DecideLog:
     (include/hd_log.h): every insert returns what decide_ordered would return
     for all the batches inserted since the last reset, joined."""
 
-    def __init__(self, v: "Verifier", height: int, f: int, schedule=None, max_entries: int = 0):
+    def __init__(self, v: "Verifier", height: int, f: int, schedule=None, max_entries: int = 0,
+                 keep_signatures: bool = False):
         self._v = v
         self._lib = v._lib
         h = ctypes.c_void_p()
@@ -327,6 +361,9 @@ class DecideLog:
         self.f = int(f)
         self._sched = None
         self._rows = 0                # rows of the last insert: the next has at most this many more than its batch
+        self.keep_signatures = bool(keep_signatures)
+        if keep_signatures:
+            v._check(self._lib.hd_log_keep_signatures(h, 1), "hd_log_keep_signatures")
         self.reset(height, f, schedule)
 
     def close(self):
@@ -387,18 +424,49 @@ class DecideLog:
         info = HdLogInfo(0, 0, 0, _ptr(logpos))
         return o, a, w, when, until, logpos, info
 
-    def _result(self, n, o, a, when, until, logpos, info, caught=None) -> LogInsertResult:
+    def _result(self, n, o, a, when, until, logpos, info, caught=None, evidence=None) -> LogInsertResult:
         self._rows = o.n
         rows = {k: a[k][: o.n].copy() for k in type(o).ROW_FIELDS}
         cls, extra = (CaughtLogInsertResult, _caught_fields(*caught)) if caught else (LogInsertResult, {})
+        if evidence:
+            ev, oa, aa = evidence
+            cls = EvidenceLogInsertResult
+            extra["evidence_offender"], extra["evidence_offender_value_ok"] = _rows_batch(ev.offender.n, oa)
+            extra["evidence_against"], extra["evidence_against_value_ok"] = _rows_batch(ev.against.n, aa)
         return cls(pclass=a["pclass"][:n].copy(), dup=a["dup"][:n].copy(), when=when[: o.n].copy(),
                    exact_until=until[: o.n].copy(), base=info.base, kept=info.kept,
                    logpos=logpos[:n].copy(), relogged=info.relogged, **rows, **extra)
 
-    def insert(self, batch: Batch, verdict: np.ndarray, value_ok=None, catch: bool = False) -> LogInsertResult:
+    def _evidence_struct(self, n: int):
+        from ._lib import HdEvidenceOut
+        off, oa = _rows_struct(n, self.keep_signatures)
+        ag, aa = _rows_struct(n, self.keep_signatures)
+        return HdEvidenceOut(off, ag), oa, aa
+
+    def read(self, positions=None, first: int = 0, n: Optional[int] = None) -> Tuple[Batch, np.ndarray]:
+        """hd_log_read: the entries ``positions`` (any order, repeats allowed),
+        or entries first .. first + n - 1 (n None: to the log's end), as
+        (Batch, value_ok bytes).  The signatures are read on a log that keeps
+        them and are zero otherwise."""
+        pos = None
+        if positions is not None:
+            pos = np.ascontiguousarray(positions, dtype=np.uint32)
+            n = len(pos)
+        elif n is None:
+            n = max(self.entries - first, 0)
+        r, a = _rows_struct(n, self.keep_signatures)
+        self._v._check(self._lib.hd_log_read(self._log, _ptr(pos), int(first), n, ctypes.byref(r)), "hd_log_read")
+        return _rows_batch(r.n, a)
+
+    def insert(self, batch: Batch, verdict: np.ndarray, value_ok=None, catch: bool = False,
+               evidence: bool = False) -> LogInsertResult:
         """hd_log_insert of a host batch with its verdicts (and value_ok, one
         byte per message, as :meth:`Verifier.decide`).  catch: also return the
-        catch list of this batch (a CaughtLogInsertResult; hd_log_insert_catch)."""
+        catch list of this batch (a CaughtLogInsertResult; hd_log_insert_catch).
+        evidence (with catch): also both whole messages of every record (an
+        EvidenceLogInsertResult; hd_log_insert_evidence)."""
+        if evidence and not catch:
+            raise ValueError("evidence=True needs catch=True")
         n = len(batch)
         verdict = np.ascontiguousarray(verdict, dtype=np.uint8)
         if len(verdict) != n:
@@ -408,6 +476,14 @@ class DecideLog:
             raise ValueError("value_ok length mismatch")
         o, a, w, when, until, logpos, info = self._outputs(n)
         cb = batch.c_struct()
+        if evidence:
+            c, ca = _catch_struct(n)
+            ev, oa, aa = self._evidence_struct(n)
+            self._v._check(self._lib.hd_log_insert_evidence(self._log, ctypes.byref(cb), _ptr(verdict), _ptr(vok),
+                                                            ctypes.byref(o), ctypes.byref(w), ctypes.byref(info),
+                                                            ctypes.byref(c), ctypes.byref(ev)),
+                           "hd_log_insert_evidence")
+            return self._result(n, o, a, when, until, logpos, info, (c, ca), (ev, oa, aa))
         if catch:
             c, ca = _catch_struct(n)
             self._v._check(self._lib.hd_log_insert_catch(self._log, ctypes.byref(cb), _ptr(verdict), _ptr(vok),
@@ -419,12 +495,14 @@ class DecideLog:
         return self._result(n, o, a, when, until, logpos, info)
 
     def insert_device(self, dbatch: HdBatch, d_bitmap: int, value_ok=None, stream: Optional[int] = None,
-                      catch: bool = False) -> LogInsertResult:
+                      catch: bool = False, evidence: bool = False) -> LogInsertResult:
         """hd_log_insert_device_bitmap over a device batch and the valid bitmap
         of verify_batch_device (bit i is message i of `dbatch`).  value_ok: a
         torch uint8 tensor on the device, or a host array, which is uploaded
-        first."""
+        first.  catch, evidence: as :meth:`insert`."""
         import torch
+        if evidence and not catch:
+            raise ValueError("evidence=True needs catch=True")
         n = dbatch.n
         vok = value_ok
         if vok is not None and not isinstance(vok, torch.Tensor):
@@ -433,6 +511,14 @@ class DecideLog:
         if vok is not None and vok.numel() != n:
             raise ValueError("value_ok length mismatch")
         o, a, w, when, until, logpos, info = self._outputs(n)
+        if evidence:
+            c, ca = _catch_struct(n)
+            ev, oa, aa = self._evidence_struct(n)
+            self._v._check(self._lib.hd_log_insert_evidence_device_bitmap(
+                self._log, ctypes.byref(dbatch), d_bitmap, vok.data_ptr() if vok is not None else None,
+                ctypes.byref(o), ctypes.byref(w), ctypes.byref(info), ctypes.byref(c), ctypes.byref(ev), stream),
+                "hd_log_insert_evidence_device_bitmap")
+            return self._result(n, o, a, when, until, logpos, info, (c, ca), (ev, oa, aa))
         if catch:
             c, ca = _catch_struct(n)
             self._v._check(self._lib.hd_log_insert_catch_device_bitmap(
@@ -881,14 +967,17 @@ class Verifier:
         return self._ordered_result(n, o, a, when, until)
 
     # ---- decide across calls -----------------------------------------
-    def open_log(self, height: int, f: int, schedule=None, max_entries: int = 0) -> DecideLog:
+    def open_log(self, height: int, f: int, schedule=None, max_entries: int = 0,
+                 keep_signatures: bool = False) -> DecideLog:
         """A device-resident log of one height on this context (hd_log):
         ``log.insert(batch, verdict)`` after ``log.insert(...)`` returns what
         :meth:`decide_ordered` would return for the batches joined.
-        max_entries: the most entries the log may hold (0: no limit).  The
-        log's inserts and this verifier's tallies and decides go on one
-        stream."""
-        return DecideLog(self, height, f, schedule, max_entries)
+        max_entries: the most entries the log may hold (0: no limit).
+        keep_signatures: each entry also keeps its 65 signature bytes, so
+        ``log.read`` and ``insert(..., catch=True, evidence=True)`` return
+        whole messages.  The log's inserts and this verifier's tallies and
+        decides go on one stream."""
+        return DecideLog(self, height, f, schedule, max_entries, keep_signatures)
 
     # ---- synthetic workload ------------------------------------------
     def gen_keys(self, S: int) -> Tuple[np.ndarray, np.ndarray]:

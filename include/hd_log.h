@@ -12,8 +12,12 @@
  * The log retains, in arrival order, every message the reference would have
  * in its logs: each logged vote (dup == 0) and each logged propose
  * (pclass == 0), with the fields decide reads (type, height, round,
- * valid_round, value, From, value_ok; no signature -- Equal ignores it).  An
- * entry's position never changes while the height lasts.  An insert replays
+ * valid_round, value, From, value_ok).  Equal ignores the signature, so a log
+ * keeps none unless hd_log_keep_signatures asks for it; with it each entry is
+ * the whole message, signature included, first-wins like every other field: a
+ * vote that arrives again with other signature bytes is a duplicate and the
+ * entry keeps the first copy's 65 bytes.  An entry's position never changes
+ * while the height lasts.  An insert replays
  * [retained entries | batch] through the ordered decide passes: first-wins is
  * "lowest index", every retained entry is the only one of its key and lies
  * below every new message, so each is logged again and the outcome is the
@@ -25,6 +29,14 @@
  * (value - base) of this batch.  A rule fired in this call exactly when its
  * `when` is >= base.  Rows are reported for every round of the height that has
  * anything logged, in the order of each round's first logged item.
+ *
+ * What the log holds can be read back (hd_log_read): a replica snapshots a
+ * height's logs with its State and, after a restart, inserts the rows it read
+ * -- with their value_ok and verdict VALID -- into a fresh log of the same
+ * height, f and schedule, which then holds the same entries at the same
+ * positions.  hd_log_insert_evidence returns, with each catch record, both
+ * whole messages the reference's Catcher takes, so the caller keeps no copy of
+ * the log to turn a log position back into a message.
  *
  * A log uses its context's tally scratch: its calls and the context's
  * tallies and decides go on one stream (the rule for tallies).  A set change
@@ -102,6 +114,53 @@ int hd_log_insert_catch(hd_log* log, const hd_batch* batch, const uint8_t* verdi
 int hd_log_insert_catch_device_bitmap(hd_log* log, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
                                       const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
                                       hd_log_info* info, hd_catch_out* caught, void* stream);
+
+/* Keep each entry's 65 signature bytes (on != 0) or not (0, the default).
+ * Allowed only while the log is empty, HD_EINVAL otherwise; the setting
+ * survives hd_log_reset.  On a log that keeps signatures every insert of
+ * n > 0 messages needs batch->sig65 (HD_EINVAL before any device work). */
+int hd_log_keep_signatures(hd_log* log, int on);
+
+/* Rows of whole messages in caller-allocated host columns of cap rows each. */
+typedef struct {
+    uint32_t cap, n;
+    uint8_t* type;
+    int64_t *height, *round, *valid_round;
+    uint8_t *value32, *from32, *value_ok;
+    uint8_t* sig65;         /* NULL: not gathered, not downloaded */
+} hd_log_rows;
+
+/* Reads n entries into out: entries first .. first + n - 1 when pos is NULL,
+ * else entries pos[0 .. n-1] (host array; any order, repeats allowed).
+ * valid_round comes back as stored: the caller's value, or -1 where the
+ * inserted batch had no valid_round array.  One gather on the device, one
+ * download, one synchronisation of the context's stream; the log is unchanged.
+ *
+ * HD_EINVAL before any device work for a NULL struct or array (sig65 apart;
+ * cap == 0 needs no arrays), cap < n, any position >= entries, or sig65 on a
+ * log that keeps no signatures.  n == 0 is HD_OK with out->n = 0. */
+int hd_log_read(hd_log* log, const uint32_t* pos, uint32_t first, uint32_t n, hd_log_rows* out);
+
+/* The inserts with the catch list, plus the evidence: row k of offender and
+ * row k of against are the whole messages of catch record k (a retained entry
+ * from the log, a message of this batch from the batch), gathered on the device
+ * in the same call.  The against row of an out-of-turn propose (against ==
+ * HD_WHEN_NEVER) is all zero bytes.  Both row sets need cap >= caught->cap
+ * (HD_EINVAL otherwise), so the only capacity error is the catch list's own;
+ * sig65 in either needs a log that keeps signatures.  Everything else -- the
+ * outputs, the errors, the log left as it was by any error -- is
+ * hd_log_insert_catch[_device_bitmap]'s. */
+typedef struct {
+    hd_log_rows offender, against;
+} hd_evidence_out;
+
+int hd_log_insert_evidence(hd_log* log, const hd_batch* batch, const uint8_t* verdict, const uint8_t* value_ok,
+                           hd_decide_out* out, hd_decide_order* order, hd_log_info* info, hd_catch_out* caught,
+                           hd_evidence_out* evidence);
+int hd_log_insert_evidence_device_bitmap(hd_log* log, const hd_batch* dbatch, const uint32_t* d_valid_bitmap,
+                                         const uint8_t* d_value_ok, hd_decide_out* out, hd_decide_order* order,
+                                         hd_log_info* info, hd_catch_out* caught, hd_evidence_out* evidence,
+                                         void* stream);
 
 #ifdef __cplusplus
 }

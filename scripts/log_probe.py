@@ -20,6 +20,18 @@ With --catch the insert is timed twice more (hd_log_insert_catch_device_bitmap):
                          replica that wants only the list pays, against
                          `insert` with both arrays
 
+With --evidence (and --catch) once more, with both whole messages of every
+record (hd_log_insert_evidence_device_bitmap):
+
+  insert_evidence        insert_catch plus the evidence rows
+
+--keep-sigs makes the log keep signatures (hd_log_keep_signatures), so every
+figure above is that of a log holding whole messages.  Where the build has
+hd_log_read, the whole log is read back at the end:
+
+  read                   hd_log_read of every entry (host wall time: the call
+                         runs on the context's stream and ends synchronised)
+
 --adv P draws the stream from a batch with P % adversarial messages, so that
 there is something to catch (0, the default, repeats messages but never
 conflicts); --only-insert leaves out decide_ordered and host_votes.
@@ -32,6 +44,7 @@ naming an older build only the entry points it has are run, so two builds can
 be compared by running the script once per build in one job.
 
     python scripts/log_probe.py [--reps 20] [--pieces 16] [--piece 8000] [--catch] [--adv 0] [--only-insert]
+                                 [--keep-sigs] [--evidence]
 """
 from __future__ import annotations
 
@@ -63,6 +76,8 @@ def main():
     ap.add_argument("--catch", action="store_true", help="also time the insert with the catch list")
     ap.add_argument("--adv", type=int, default=0, help="adversarial messages in the source batch, per cent")
     ap.add_argument("--only-insert", action="store_true", help="leave out decide_ordered and host_votes")
+    ap.add_argument("--keep-sigs", action="store_true", help="the log keeps signatures (hd_log_keep_signatures)")
+    ap.add_argument("--evidence", action="store_true", help="with --catch: also time the insert with evidence")
     a = ap.parse_args()
     if a.piece % 32:
         raise SystemExit("log_probe: --piece must be a multiple of 32 (the bitmap is sliced by words)")
@@ -127,7 +142,10 @@ def main():
 
     # the retained log
     if hasattr(lib, "hd_log_insert_device_bitmap"):
-        log = v.open_log(1, f, ks[0])
+        if a.keep_sigs and not hasattr(lib, "hd_log_keep_signatures"):
+            raise SystemExit("log_probe: --keep-sigs needs a build with hd_log_keep_signatures")
+        log = v.open_log(1, f, ks[0], keep_signatures=a.keep_sigs)
+        out["keep_sigs"] = a.keep_sigs
         o2, _oa2 = v._decide_struct(m, distinct + m)            # rows: at most one per distinct message
         w2, _w2, _u2 = v._order_struct(distinct + m)
         logpos = np.zeros(m, np.uint32)
@@ -171,6 +189,34 @@ def main():
                             dev[k].append(d)
                 out[key] = med(dev)
                 assert out.setdefault("caught", caught) == caught   # the same records either way
+            if a.evidence and hasattr(lib, "hd_log_insert_evidence_device_bitmap"):
+                e, _eo, _ea = log._evidence_struct(m)
+                dev = [[] for _ in range(P)]
+                for rep in range(a.warm + a.reps):
+                    log.reset(1)
+                    for k, (cs, bm) in enumerate(parts):
+                        def call():
+                            rc = lib.hd_log_insert_evidence_device_bitmap(log.handle, ctypes.byref(cs), bm, None,
+                                                                          ctypes.byref(o2), ctypes.byref(w2),
+                                                                          ctypes.byref(info), ctypes.byref(c),
+                                                                          ctypes.byref(e), s)
+                            assert rc == 0, rc
+                        d, _ = timed(call)
+                        assert e.offender.n == e.against.n == c.n == out["caught"][k]
+                        if rep >= a.warm:
+                            dev[k].append(d)
+                out["insert_evidence_ms"] = med(dev)
+        if hasattr(lib, "hd_log_read"):   # every loop above leaves the log full
+            from hyperdrive_amd.verify import _rows_struct
+            L = log.entries
+            r, _ra = _rows_struct(L, a.keep_sigs)
+            wall = []
+            for rep in range(a.warm + a.reps):
+                t0 = time.perf_counter()
+                rc = lib.hd_log_read(log.handle, None, 0, L, ctypes.byref(r))
+                wall.append((time.perf_counter() - t0) * 1e3)
+                assert rc == 0 and r.n == L, rc
+            out.update(read_entries=L, read_ms=round(float(np.median(wall[a.warm:])), 4))
         log.close()
 
     if not a.only_insert:
