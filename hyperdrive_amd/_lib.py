@@ -148,6 +148,10 @@ SIGNATURES = {
     "hd_ctx_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_ctx_set_pubkey_format": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "hd_set_signatories": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "hd_import_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                      ctypes.c_void_p]),
+    "hd_export_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                      ctypes.POINTER(ctypes.c_uint32)]),
     "hd_ctx_set_fastpath": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "hd_ctx_fastpath_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                              ctypes.POINTER(ctypes.c_uint32)]),
@@ -258,6 +262,10 @@ SIGNATURES = {
     "hd_multi_ctx": (ctypes.c_void_p, [ctypes.c_void_p, ctypes.c_int]),
     "hd_multi_set_signatories": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
     "hd_multi_set_pubkey_format": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "hd_multi_import_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                            ctypes.c_void_p]),
+    "hd_multi_export_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.POINTER(ctypes.c_uint32)]),
     "hd_multi_verify_batch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "hd_route_candidates_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,

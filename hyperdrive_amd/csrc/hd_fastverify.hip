@@ -1884,6 +1884,20 @@ int hd_fb_clear_keys(hd_ctx* ctx) {
     return fb_count_not_ready(ctx);
 }
 
+bool hd_fb_key_view(const hd_ctx* ctx, FbKeyView* v) {
+    const FbWork* f = ctx->fb;
+    if (!f || !ctx->n_adm || !f->adm_slot || !f->map_ok || !f->state || !f->pub) return false;
+    *v = FbKeyView{f->state, f->pub, f->adm_slot, f->nslots};
+    return true;
+}
+
+int hd_fb_learn_sync(hd_ctx* ctx) {
+    int rc = fb_learn(ctx, ctx->stream);
+    if (rc) return rc;
+    FBCHK(hipStreamSynchronize(ctx->stream), "fb key import");
+    return fb_count_not_ready(ctx);
+}
+
 // the next free event pair of a profile record (created on first use), or
 // NULL when profiling is off or the event could not be created
 static hipEvent_t* fb_prof_pair(std::vector<hipEvent_t>& ev, size_t& used, bool on) {

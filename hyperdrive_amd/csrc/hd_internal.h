@@ -147,6 +147,22 @@ int hd_fb_clear_keys(hd_ctx* ctx);               // pubkey format changed: learn
 int hd_fb_verify(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest, uint8_t* d_verdict, uint8_t* d_rec32,
                  int32_t* d_signer, uint32_t* d_bitmap, hipStream_t s, bool auth = false);
 
+// The key slots as hd_import_keys / hd_export_keys (hd_keyimport.hip) see
+// them: the state machine k_verify publishes into, the admitted slot map and
+// the number of slots with a table.  false: the context has no usable slot
+// map (no fast path, no admitted set, or the last table mapping failed).
+struct FbKeyView {
+    uint32_t* state;
+    hd::ge* pub;
+    const int32_t* adm_slot;
+    uint32_t nslots;
+};
+bool hd_fb_key_view(const hd_ctx* ctx, FbKeyView* v);
+// Build the tables of every LEARNED slot on the context's stream, wait, and
+// set the not-ready count exactly: the next verify call then launches no
+// builder kernels when nothing is left to learn.
+int hd_fb_learn_sync(hd_ctx* ctx);
+
 // slow-path control for k_verify (hd_verify.hip): an index list and key learning
 struct SlowCtl {
     const uint32_t* list;   // message indices to verify, or NULL for all

@@ -381,6 +381,51 @@ int hd_multi_set_pubkey_format(hd_multi* m, int format) {
     return HD_OK;
 }
 
+int hd_multi_import_keys(hd_multi* m, const uint8_t* keys64, uint32_t n, uint8_t* status, int32_t* signer) {
+    if (!m) return HD_EINVAL;
+    if (n == 0) return HD_OK;
+    if (!keys64 || !status) return HD_EINVAL;
+    // context 0 writes the caller's arrays, the others their own: the
+    // contexts hold the same admitted set, so they must agree row by row
+    const int G = (int)m->dev.size();
+    std::vector<std::vector<uint8_t>> st(G);
+    std::vector<std::vector<int32_t>> sg(G);
+    for (int k = 1; k < G; k++) {
+        st[k].resize(n);
+        sg[k].resize(n);
+    }
+    int rc = on_all_devices(m, [&](Dev& d, int k) {
+        return hd_import_keys(d.ctx, keys64, n, k ? st[k].data() : status, k ? sg[k].data() : signer);
+    });
+    if (rc) return rc;
+    for (int k = 1; k < G; k++)
+        if (memcmp(st[k].data(), status, n) != 0 || (signer && memcmp(sg[k].data(), signer, 4 * (size_t)n) != 0)) {
+            m->dev[0].ctx->last_error = "hd_multi_import_keys: the contexts disagree on a key's status";
+            return HD_EDEVICE;
+        }
+    return HD_OK;
+}
+
+int hd_multi_export_keys(hd_multi* m, uint8_t* keys64, uint8_t* known, uint32_t cap, uint32_t* n_out) {
+    if (!m || m->dev.empty()) return HD_EINVAL;
+    int rc = hd_export_keys(m->dev[0].ctx, keys64, known, cap, n_out);
+    if (rc || *n_out == 0) return rc;
+    const uint32_t n = *n_out;
+    std::vector<uint8_t> k64(64 * (size_t)n), kn(n);
+    for (size_t k = 1; k < m->dev.size(); k++) {
+        uint32_t nk = 0;
+        rc = hd_export_keys(m->dev[k].ctx, k64.data(), kn.data(), n, &nk);
+        if (rc) return rc;
+        if (nk != n) return HD_EDEVICE;
+        for (uint32_t i = 0; i < n; i++)
+            if (kn[i] && !known[i]) {
+                known[i] = 1;
+                memcpy(keys64 + 64 * (size_t)i, &k64[64 * (size_t)i], 64);
+            }
+    }
+    return HD_OK;
+}
+
 }  // extern "C"
 
 namespace {

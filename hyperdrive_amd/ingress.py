@@ -271,12 +271,21 @@ class Ingress:
         if self.log is not None:
             self.log.reset(self.height)
 
-    def reset_height(self, height: int, signatories=None) -> bool:
+    def export_keys(self):
+        """Verifier.export_keys: the public keys known so far, in the order
+        of the signatory set, to save with a State snapshot and hand back to
+        :meth:`reset_height` after a restart."""
+        return self.v.export_keys()
+
+    def reset_height(self, height: int, signatories=None, keys=None) -> bool:
         """Replica.ResetHeight (replica.go:216-235): ignored (returns False)
         unless `height` is above the current height (:223-225).  Otherwise the
         ResetHeightMessage (:132-145): the logs restart at `height`, lower
         heights leave the queue, and a non-empty signatory set replaces
-        procsAllowed (the verifier's admitted set) and f."""
+        procsAllowed (the verifier's admitted set) and f.  keys: public keys
+        (rows of 64 bytes, X || Y) imported after the set change
+        (Verifier.import_keys: untrusted, each must hash to an admitted
+        signatory), so the first push authenticates against known keys."""
         if int(height) <= self.height:
             return False
         self.height = int(height)
@@ -287,6 +296,8 @@ class Ingress:
         if signatories is not None and len(signatories):
             self.v.set_signatories(signatories)
             self._set_f(len(signatories) // 3)
+        if keys is not None and len(keys):
+            self.v.import_keys(keys)
         if self.log is not None:
             self.log.reset(self.height, self.f or 0)
         return True

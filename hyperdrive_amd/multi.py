@@ -33,6 +33,7 @@ class MultiVerifier:
         self._close_rank = 1
         _lib.track(self)
         self.devices = [int(d) for d in devs]
+        self.n_signatories = 0
         self._check(self._lib.hd_multi_set_pubkey_format(self._m, int(compressed)), "hd_multi_set_pubkey_format")
 
     def _check(self, rc: int, where: str):
@@ -61,6 +62,27 @@ class MultiVerifier:
     def set_signatories(self, signatories) -> None:
         arr = _as_rows(signatories, 32)
         self._check(self._lib.hd_multi_set_signatories(self._m, _ptr(arr), len(arr)), "hd_multi_set_signatories")
+        self.n_signatories = len(arr)
+
+    def import_keys(self, keys) -> Tuple[np.ndarray, np.ndarray]:
+        """hd_multi_import_keys: Verifier.import_keys on every context."""
+        arr = _as_rows(keys, 64)
+        n = len(arr)
+        status = np.zeros(n, np.uint8)
+        signer = np.full(n, -1, np.int32)
+        self._check(self._lib.hd_multi_import_keys(self._m, _ptr(arr), n, _ptr(status), _ptr(signer)),
+                    "hd_multi_import_keys")
+        return status, signer
+
+    def export_keys(self) -> Tuple[np.ndarray, np.ndarray]:
+        """hd_multi_export_keys: Verifier.export_keys over the contexts (a key
+        any context knows is known)."""
+        cap, n = self.n_signatories, ctypes.c_uint32()
+        keys = np.zeros((cap, 64), np.uint8)
+        known = np.zeros(cap, np.uint8)
+        self._check(self._lib.hd_multi_export_keys(self._m, _ptr(keys), _ptr(known), cap, ctypes.byref(n)),
+                    "hd_multi_export_keys")
+        return keys[: n.value], known[: n.value].astype(bool)
 
     def fastpath_stats(self, k: int = 0) -> Tuple[int, int]:
         known, fb = ctypes.c_uint32(), ctypes.c_uint32()

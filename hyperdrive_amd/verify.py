@@ -42,6 +42,9 @@ VERDICT_NAMES = ["VALID", "BAD_RECID", "BAD_RS", "NO_POINT", "INFINITY", "SIGNAT
 
 PROPOSE, PREVOTE, PRECOMMIT = 1, 2, 3
 
+# statuses of import_keys (include/hd_verify.h HD_KEY_*)
+KEY_IMPORTED, KEY_KNOWN, KEY_NOT_ADMITTED, KEY_NO_SLOT, KEY_BAD_POINT = 0, 1, 2, 3, 4
+
 
 def _ptr(a: Optional[np.ndarray]):
     if a is None:
@@ -584,6 +587,41 @@ class Verifier:
         arr = _as_rows(signatories, 32)
         self._check(self._lib.hd_set_signatories(self._ctx, _ptr(arr), len(arr)), "hd_set_signatories")
         self.n_signatories = len(arr)
+
+    def set_pubkey_format(self, fmt) -> None:
+        """hd_ctx_set_pubkey_format (values as ``compressed`` of the
+        constructor); a change drops every known key, imported ones included."""
+        self._check(self._lib.hd_ctx_set_pubkey_format(self._ctx, int(fmt)), "hd_ctx_set_pubkey_format")
+
+    def import_keys(self, keys) -> Tuple[np.ndarray, np.ndarray]:
+        """hd_import_keys: public keys (rows of 64 bytes, X || Y big-endian) of
+        admitted signatories, so that their messages take the known-key check
+        from the first batch on.  Returns (status uint8[n] of KEY_*, signer
+        int32[n]: the row of the signatory array, -1 for a key that is not
+        admitted or not a curve point).  The keys are not trusted: each is
+        hashed in the context's pubkey format and looked up in the admitted
+        set."""
+        arr = _as_rows(keys, 64)
+        n = len(arr)
+        status = np.zeros(n, np.uint8)
+        signer = np.full(n, -1, np.int32)
+        self._check(self._lib.hd_import_keys(self._ctx, _ptr(arr), n, _ptr(status), _ptr(signer)), "hd_import_keys")
+        return status, signer
+
+    def export_keys(self) -> Tuple[np.ndarray, np.ndarray]:
+        """hd_export_keys: (keys uint8[n, 64], known bool[n]) for the n rows of
+        the signatory array last given to set_signatories; a row whose key is
+        not known yet is zero."""
+        cap, n = self.n_signatories, ctypes.c_uint32()
+        while True:
+            keys = np.zeros((cap, 64), np.uint8)
+            known = np.zeros(cap, np.uint8)
+            rc = self._lib.hd_export_keys(self._ctx, _ptr(keys), _ptr(known), cap, ctypes.byref(n))
+            if rc != -4 or n.value <= cap:   # HD_ECAP: the set is larger than this object last saw
+                break
+            cap = n.value
+        self._check(rc, "hd_export_keys")
+        return keys[: n.value], known[: n.value].astype(bool)
 
     # include/hd_verify.h HD_VAR_*: kernel variants of this context
     VARIANTS = {"verify_waves": 0, "sum_waves": 1, "sum_prefetch": 2, "split_k": 4, "recover_g": 5,

@@ -132,6 +132,41 @@ int hd_ctx_set_pubkey_format(hd_ctx* ctx, int format);
  * still learning keys must not see its slots reassigned), so call it between
  * batches, as ResetHeight does (replica/replica.go:136-144). */
 int hd_set_signatories(hd_ctx* ctx, const uint8_t* sigs32, uint32_t n);
+/* Public keys of admitted signatories, supplied by the caller (a replica
+ * holds its peers' keys, or exported them before it stopped), so that the
+ * known-key fast path below does not start cold after a restart, a format
+ * change or a set change.  The keys are not trusted: a signatory is SHA-256
+ * of its key's encoding, so each key is checked to lie on the curve, hashed
+ * in the context's pubkey format and looked up in the admitted set; a key
+ * that hashes to no admitted signatory is not stored.  An import changes no
+ * output of any verify or authenticate call: it only makes a signatory's key
+ * known before its first VALID message instead of after it.
+ * Both calls wait for the context's device work in flight and are synchronous
+ * (call them between batches, as hd_set_signatories).  Imported keys are kept
+ * and dropped exactly as learned ones (kept across hd_set_signatories for
+ * signatories that stay admitted; dropped by a pubkey format change and when
+ * a set change picks another table width). */
+#define HD_KEY_IMPORTED     0  /* slot was empty: key stored, tables built               */
+#define HD_KEY_KNOWN        1  /* slot already had a key (necessarily this one)          */
+#define HD_KEY_NOT_ADMITTED 2  /* SHA-256(encoding) is not in the admitted set           */
+#define HD_KEY_NO_SLOT      3  /* admitted, but no table slot (budget, fast path off,
+                                  or the last table mapping failed)                      */
+#define HD_KEY_BAD_POINT    4  /* X or Y >= p, or Y^2 != X^3 + 7 (includes (0,0))        */
+/* keys64: n x 64 bytes, X || Y, 32-byte big-endian each, on host memory,
+ * whatever the pubkey format (the format only decides how the key is hashed).
+ * status: n bytes (HD_KEY_*), decided by the slots' states before the call:
+ * rows that repeat one key report the same status.  signer: n int32 or NULL:
+ * index into the array last given to hd_set_signatories (as the verify calls
+ * report it), -1 unless status <= 3 and the key is admitted.  On return every
+ * IMPORTED key's tables are built.  HD_EINVAL, before any device work, for a
+ * NULL keys64 or status with n > 0; n == 0 is HD_OK. */
+int hd_import_keys(hd_ctx* ctx, const uint8_t* keys64, uint32_t n, uint8_t* status, int32_t* signer);
+/* For each of the n_adm entries of the array last given to hd_set_signatories
+ * (duplicates included): known[i] = 1 and keys64[64 i ..] = X || Y when that
+ * signatory's slot holds a key (learned or imported), else 0 and 64 zero
+ * bytes.  *n_out = n_adm.  cap < n_adm: HD_ECAP with *n_out = n_adm, nothing
+ * written. */
+int hd_export_keys(hd_ctx* ctx, uint8_t* keys64, uint8_t* known, uint32_t cap, uint32_t* n_out);
 /* Known-key fast path (on by default; HD_VERIFY_FASTPATH=0 in the
  * environment turns it off for new contexts).  The first message of an
  * admitted signatory that verifies VALID through the full recovery teaches
@@ -652,6 +687,11 @@ int hd_multi_size(hd_multi* m, int* ngpus, int* uses_rccl);
 hd_ctx* hd_multi_ctx(hd_multi* m, int k);
 int hd_multi_set_signatories(hd_multi* m, const uint8_t* sigs32, uint32_t n);
 int hd_multi_set_pubkey_format(hd_multi* m, int format);
+/* hd_import_keys on every context; HD_EDEVICE when the contexts disagree on a
+ * status.  hd_export_keys over the contexts: known ORed, each key from the
+ * first context that has it. */
+int hd_multi_import_keys(hd_multi* m, const uint8_t* keys64, uint32_t n, uint8_t* status, int32_t* signer);
+int hd_multi_export_keys(hd_multi* m, uint8_t* keys64, uint8_t* known, uint32_t cap, uint32_t* n_out);
 int hd_multi_verify_batch(hd_multi* m, const hd_batch* batch, uint8_t* verdict, uint8_t* recovered32,
                           uint32_t* valid_bitmap, hd_tally_out* tally);
 
