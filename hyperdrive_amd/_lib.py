@@ -91,6 +91,12 @@ class HdTallyOut(ctypes.Structure):
     ]
 
 
+class HdSetChangeInfo(ctypes.Structure):
+    """include/hd_verify.h hd_set_change_info."""
+    _fields_ = [("width_before", ctypes.c_int), ("width_after", ctypes.c_int), ("kept", ctypes.c_uint32),
+                ("carried", ctypes.c_uint32), ("dropped", ctypes.c_uint32)]
+
+
 class HdDecideIn(ctypes.Structure):
     """include/hd_verify.h hd_decide_in."""
     _fields_ = [("f", ctypes.c_uint32), ("n_sched", ctypes.c_uint32), ("sched32", ctypes.c_void_p),
@@ -152,6 +158,7 @@ SIGNATURES = {
                                       ctypes.c_void_p]),
     "hd_export_keys": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
                                       ctypes.POINTER(ctypes.c_uint32)]),
+    "hd_ctx_set_change_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdSetChangeInfo)]),
     "hd_ctx_set_fastpath": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     "hd_ctx_fastpath_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32),
                                              ctypes.POINTER(ctypes.c_uint32)]),

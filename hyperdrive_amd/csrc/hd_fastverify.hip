@@ -39,6 +39,7 @@
 #include "hd_dedup.h"
 #include "hd_scmont.h"
 #include "hd_internal.h"
+#include "hd_keycarry.h"
 #include "hd_verify_msg.h"
 
 using namespace hd;
@@ -169,6 +170,7 @@ struct FbWork {
     size_t n_call = 0, n_sums = 0;   // pairs in use
     std::unordered_map<std::string, uint32_t> slot_of;  // signatory -> slot
     std::vector<uint32_t> free_slots;
+    hd_set_change_info change{0, 0, 0, 0, 0};   // hd_ctx_set_change_info: the last hd_fb_map_signatories
     uint32_t used = 1;            // slots handed out so far (slot 0 = G)
     int wp = HD_FB_W;             // window width of the per-key tables (HD_FB_W or HD_FB_WW)
     int last_k = 8;               // messages per inversion of the last split check (FbCallPlan::k)
@@ -1740,7 +1742,49 @@ static int fb_count_not_ready(hd_ctx* ctx) {
     return HD_OK;
 }
 
-static int fb_map(hd_ctx* ctx, const uint8_t* sorted, uint32_t m, int cap);
+// What hd_fb_map_signatories knew at its entry, before its first attempt
+// (hd_keycarry.h): the signatories with a slot, sorted, and every slot's
+// state.  A failed attempt leaves slot_of with slots of departed signatories
+// handed to new ones while their states still say READY, so this copy -- never
+// slot_of -- is what a later attempt of the same call carries keys from.
+struct FbSnapshot {
+    std::vector<uint8_t> sig32;
+    std::vector<uint32_t> slot, state;
+    uint32_t f0 = 0, f1 = 0;
+    uint32_t known = 0, staying = 0;   // its known keys, and those whose signatory is in the new set
+    bool carry = false;     // the context picks its own width: known keys cross a re-tier
+    bool gathered = false;   // stash holds the keys (the first attempt that frees the tables gathers)
+    FbKeyStash stash;
+    KeySnapshot view() const {
+        return KeySnapshot{sig32.data(), slot.data(), (uint32_t)slot.size(), state.data(), (uint32_t)state.size(), f0, f1};
+    }
+};
+
+static int fb_snapshot(hd_ctx* ctx, FbSnapshot& sn) {
+    FbWork* f = ctx->fb;
+    int rq = hd_ctx_quiesce(ctx);
+    if (rq) return rq;
+    sn.carry = ctx->var[HD_VAR_KEY_WIDTH] == 0;
+    // (after a failed mapping nothing is known: it forgot the keys)
+    if (!f->map_ok || !f->state || !f->pub || f->nslots < 2 || f->slot_of.empty()) return HD_OK;
+    std::vector<std::pair<std::string, uint32_t>> rows(f->slot_of.begin(), f->slot_of.end());
+    std::sort(rows.begin(), rows.end());
+    sn.sig32.resize(32 * rows.size());
+    sn.slot.resize(rows.size());
+    for (size_t r = 0; r < rows.size(); r++) {
+        memcpy(&sn.sig32[32 * r], rows[r].first.data(), 32);
+        sn.slot[r] = rows[r].second;
+    }
+    sn.f0 = f->fbase;
+    sn.f1 = f->fbase + f->fres;
+    sn.state.resize(f->nslots);
+    FBCHK(hipMemcpyAsync(sn.state.data(), f->state, 4 * (size_t)f->nslots, hipMemcpyDeviceToHost, ctx->stream),
+          "fb state snapshot");
+    FBCHK(hipStreamSynchronize(ctx->stream), "fb state snapshot");
+    return HD_OK;
+}
+
+static int fb_map(hd_ctx* ctx, const uint8_t* sorted, uint32_t m, int cap, FbSnapshot& sn);
 
 // HD_FB_TRACE=1: one stderr line per table-mapping attempt (debug aid)
 static bool fb_trace() {
@@ -1756,12 +1800,18 @@ static std::mutex g_fb_map_mutex[64];
 
 // Map the admitted set to table slots.  A table allocation the device
 // cannot serve (another process took the memory since the width was picked)
-// retries at the next narrower width, down to 13 bits, instead of failing
-// the set change.
+// retries at the next width below the one that failed, down to 13 bits,
+// instead of failing the set change.  The keys known at entry (the snapshot)
+// survive every attempt that ends in a successful mapping.
 int hd_fb_map_signatories(hd_ctx* ctx, const uint8_t* sorted, uint32_t m) {
     std::lock_guard<std::mutex> lock(g_fb_map_mutex[(unsigned)ctx->device % 64u]);
-    int rc = HD_OK;
-    for (int cap : {0, HD_FB_WW, HD_FB_W, HD_FB_WN}) {
+    FbWork* f = ctx->fb;
+    FbSnapshot sn;
+    int rc = fb_snapshot(ctx, sn);
+    if (!rc) key_snap_count(sn.view(), sorted, m, sn.known, sn.staying);
+    // (until an attempt succeeds: every known key is lost)
+    f->change = hd_set_change_info{f->wp, f->wp, 0, 0, sn.known};
+    for (int cap = 0; rc == HD_OK || cap;) {   // (a failed snapshot: no attempt)
         if (fb_trace()) {
             size_t fr = 0, tot = 0;
             (void)hipMemGetInfo(&fr, &tot);
@@ -1769,21 +1819,34 @@ int hd_fb_map_signatories(hd_ctx* ctx, const uint8_t* sorted, uint32_t m) {
                     (void*)ctx, m, cap, ctx->fb->wp, ctx->fb->nslots, ctx->fb->used, ctx->fb->max_slots,
                     ctx->fb->bytes / 1e9, fb_device_bytes(ctx->device) / 1e9, fr / 1e9);
         }
-        rc = fb_map(ctx, sorted, m, cap);
+        rc = fb_map(ctx, sorted, m, cap, sn);
         if (fb_trace())
             fprintf(stderr, "[fb] ctx %p -> rc %d wp %d nslots %u used %u %s\n", (void*)ctx, rc, ctx->fb->wp,
                     ctx->fb->nslots, ctx->fb->used, rc ? ctx->last_error.c_str() : "");
         if (rc != HD_ENOMEM || ctx->var[HD_VAR_KEY_WIDTH]) break;
         (void)hipGetLastError();   // the failed allocation must not surface in a later launch check
+        // the next width below the one that just failed: every retry is narrower
+        const int failed = f->wp;
+        cap = failed > HD_FB_WW ? HD_FB_WW : failed > HD_FB_W ? HD_FB_W : failed > HD_FB_WN ? HD_FB_WN : 0;
+        if (!cap) break;
     }
+    hd_key_stash_free(&sn.stash);
     // a set change that failed here leaves slots mapped without tables (and
     // the device's slot map of the previous set): until a mapping succeeds,
     // every message takes the full recovery against the new admitted set
-    ctx->fb->map_ok = rc == HD_OK;
+    f->map_ok = rc == HD_OK;
+    f->change.width_after = f->wp;
+    if (!f->map_ok && f->state) {
+        // and it forgets the keys: its attempts handed slots of departed
+        // signatories to new ones without resetting their states
+        (void)hipMemsetAsync(f->state, 0, 4 * (size_t)f->max_slots, ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipGetLastError();
+    }
     return rc;
 }
 
-static int fb_map(hd_ctx* ctx, const uint8_t* sorted, uint32_t m, int cap) {
+static int fb_map(hd_ctx* ctx, const uint8_t* sorted, uint32_t m, int cap, FbSnapshot& sn) {
     FbWork* f = ctx->fb;
     // no verify call of this context may still learn into a slot reassigned
     // here (hd_set_signatories quiesced the context already)
@@ -1791,8 +1854,22 @@ static int fb_map(hd_ctx* ctx, const uint8_t* sorted, uint32_t m, int cap) {
     if (rq) return rq;
     *(volatile uint32_t*)f->nr_host = 0xFFFFFFFFu;
     const int wp = fb_pick_width(ctx, m, cap);
-    if (wp != f->wp || (cap && f->nslots < f->used)) {
-        // another table width: every key is learned again (full recovery)
+    const bool retier = wp != f->wp;
+    std::vector<int32_t> adm_slot(std::max(m, 1u), -1);
+    std::vector<uint32_t> fresh;
+    KeyCarryPlan plan;
+    if (retier) {
+        // Another table width: the tables go, and the key and state arrays
+        // with them.  When the context picks its own width the keys known at
+        // the call's entry cross this step in a stash of their own, gathered
+        // once, before the first free; with a forced width (HD_VAR_KEY_WIDTH)
+        // every key is learned again (full recovery).
+        if (sn.carry && !sn.gathered && !sn.slot.empty()) {
+            const FbKeyView old{f->state, f->pub, nullptr, (uint32_t)sn.state.size()};
+            int rg = hd_key_stash_gather(ctx, sn.slot.data(), (uint32_t)sn.slot.size(), old, sn.f0, sn.f1, &sn.stash);
+            if (rg) return rg;
+            sn.gathered = true;
+        }
         fb_free_tables(ctx);
         f->slot_of.clear();
         f->free_slots.clear();
@@ -1804,38 +1881,48 @@ static int fb_map(hd_ctx* ctx, const uint8_t* sorted, uint32_t m, int cap) {
         int ra = fb_alloc_slots(ctx);
         if (ra) return ra;
     }
-    std::unordered_map<std::string, uint32_t> keep;
-    std::vector<int32_t> adm_slot(std::max(m, 1u), -1);
-    std::vector<uint32_t> fresh;
-    for (uint32_t k = 0; k < m; k++) {
-        std::string key(reinterpret_cast<const char*>(sorted + 32 * (size_t)k), 32);
-        auto it = f->slot_of.find(key);
-        if (it != f->slot_of.end()) {
-            adm_slot[k] = (int32_t)it->second;
-            keep.emplace(key, it->second);
-            f->slot_of.erase(it);
+    if (retier && sn.gathered) {
+        // the carried signatories take slots first (hd_keycarry.h); every
+        // state is EMPTY already (fb_alloc_slots)
+        key_carry_plan(sn.view(), sorted, m, f->max_slots, plan);
+        adm_slot = plan.adm_slot;
+        for (uint32_t k = 0; k < m; k++)
+            if (adm_slot[k] >= 0)
+                f->slot_of.emplace(std::string(reinterpret_cast<const char*>(sorted + 32 * (size_t)k), 32),
+                                   (uint32_t)adm_slot[k]);
+        f->used = plan.used;
+    } else {
+        std::unordered_map<std::string, uint32_t> keep;
+        for (uint32_t k = 0; k < m; k++) {
+            std::string key(reinterpret_cast<const char*>(sorted + 32 * (size_t)k), 32);
+            auto it = f->slot_of.find(key);
+            if (it != f->slot_of.end()) {
+                adm_slot[k] = (int32_t)it->second;
+                keep.emplace(key, it->second);
+                f->slot_of.erase(it);
+            }
         }
-    }
-    // signatories no longer admitted give their slots back
-    for (auto& kv : f->slot_of) {
-        f->free_slots.push_back(kv.second);
-        fresh.push_back(kv.second);
-    }
-    f->slot_of.swap(keep);
-    for (uint32_t k = 0; k < m; k++) {
-        if (adm_slot[k] >= 0) continue;
-        uint32_t slot;
-        if (!f->free_slots.empty()) {
-            slot = f->free_slots.back();
-            f->free_slots.pop_back();
-        } else if (f->used < f->max_slots) {
-            slot = f->used++;
-        } else {
-            continue;  // over the slot cap: this signatory always takes the full recovery
+        // signatories no longer admitted give their slots back
+        for (auto& kv : f->slot_of) {
+            f->free_slots.push_back(kv.second);
+            fresh.push_back(kv.second);
         }
-        adm_slot[k] = (int32_t)slot;
-        f->slot_of.emplace(std::string(reinterpret_cast<const char*>(sorted + 32 * (size_t)k), 32), slot);
-        fresh.push_back(slot);
+        f->slot_of.swap(keep);
+        for (uint32_t k = 0; k < m; k++) {
+            if (adm_slot[k] >= 0) continue;
+            uint32_t slot;
+            if (!f->free_slots.empty()) {
+                slot = f->free_slots.back();
+                f->free_slots.pop_back();
+            } else if (f->used < f->max_slots) {
+                slot = f->used++;
+            } else {
+                continue;  // over the slot cap: this signatory always takes the full recovery
+            }
+            adm_slot[k] = (int32_t)slot;
+            f->slot_of.emplace(std::string(reinterpret_cast<const char*>(sorted + 32 * (size_t)k), 32), slot);
+            fresh.push_back(slot);
+        }
     }
     // foreign keys: a block of slots reserved once, after the admitted ones
     // of the first set that asks for it; emptied (dictionary and states) on
@@ -1866,7 +1953,22 @@ static int fb_map(hd_ctx* ctx, const uint8_t* sorted, uint32_t m, int cap) {
     if (rc) return rc;
     FBCHK(hipMemcpyAsync(f->adm_slot, adm_slot.data(), 4 * adm_slot.size(), hipMemcpyHostToDevice, s), "fb adm_slot");
     FBCHK(hipStreamSynchronize(s), "fb map");
-    return fb_count_not_ready(ctx);
+    if (!plan.carry.empty()) {
+        // the carried keys into their new slots (after the resets above), and
+        // their tables at the new width before the call returns: the next
+        // verify call finds them READY and launches no builder kernel for them
+        const FbKeyView now{f->state, f->pub, f->adm_slot, f->nslots};
+        rc = hd_key_stash_carry(ctx, sn.stash, plan.carry.data(), (uint32_t)plan.carry.size(), now);
+        if (!rc) rc = fb_learn(ctx, s);   // (nr_host is UINT32_MAX: the build runs)
+        if (rc) return rc;
+        FBCHK(hipStreamSynchronize(s), "fb key carry");
+    }
+    rc = fb_count_not_ready(ctx);
+    if (rc) return rc;
+    f->change.kept = retier ? 0 : sn.staying;
+    f->change.carried = plan.carried;
+    f->change.dropped = sn.known - f->change.kept - f->change.carried;
+    return HD_OK;
 }
 
 int hd_fb_clear_keys(hd_ctx* ctx) {
@@ -2234,6 +2336,12 @@ int hd_ctx_fastpath_stats(hd_ctx* ctx, uint32_t* known_keys, uint32_t* last_fall
     }
     if (last_fallback && f->last_set >= 0)
         FBCHK(hipMemcpy(last_fallback, f->sc[f->last_set].count, 4, hipMemcpyDeviceToHost), "fallback read");
+    return HD_OK;
+}
+
+int hd_ctx_set_change_info(hd_ctx* ctx, hd_set_change_info* out) {
+    if (!ctx || !out) return HD_EINVAL;
+    *out = ctx->fb && ctx->fastpath ? ctx->fb->change : hd_set_change_info{0, 0, 0, 0, 0};
     return HD_OK;
 }
 

@@ -163,6 +163,24 @@ bool hd_fb_key_view(const hd_ctx* ctx, FbKeyView* v);
 // builder kernels when nothing is left to learn.
 int hd_fb_learn_sync(hd_ctx* ctx);
 
+// The key carry of a re-tiering set change (hd_keyimport.hip, hd_keycarry.h):
+// one stash row per snapshot row -- the key of its old slot and whether that
+// slot held one -- in allocations of their own, since the key and state
+// arrays go with the tables.  gather: before the tables are freed (`old`:
+// the arrays about to go, nslots = how many states they hold; [f0, f1) the
+// foreign block); carry: rows into their new slots as LEARNED, after the new
+// arrays exist and their states are reset.  Both wait for the stream.
+struct FbKeyStash {
+    hd::ge* key = nullptr;
+    uint32_t* words = nullptr;   // n flags, then 2 n index words
+    uint32_t n = 0;
+};
+int hd_key_stash_gather(hd_ctx* ctx, const uint32_t* snap_slot, uint32_t n, const FbKeyView& old, uint32_t f0,
+                        uint32_t f1, FbKeyStash* st);
+int hd_key_stash_carry(hd_ctx* ctx, const FbKeyStash& st, const std::pair<uint32_t, uint32_t>* carry, uint32_t n,
+                       const FbKeyView& now);
+void hd_key_stash_free(FbKeyStash* st);
+
 // slow-path control for k_verify (hd_verify.hip): an index list and key learning
 struct SlowCtl {
     const uint32_t* list;   // message indices to verify, or NULL for all

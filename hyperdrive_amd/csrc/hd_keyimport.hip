@@ -13,7 +13,11 @@
 //                  key one wins the CAS; the others carry the same key.
 //   fb_learn       builds the tables of the LEARNED slots (hd_fb_learn_sync).
 // Export is one gather kernel and one download.  Neither is a throughput
-// kernel: a replica calls them once per restart or set change.
+// kernel: a replica calls them once per restart or format change.
+//
+// The key carry (hd_keycarry.h) lives here too: k_key_gather and k_key_carry
+// take the known keys over a set change that frees the tables (fb_map in
+// hd_fastverify.hip calls hd_key_stash_*).  Those keys stay on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -103,11 +107,92 @@ __global__ __launch_bounds__(256) void k_key_export(const uint8_t* __restrict__ 
     }
 }
 
+// The key carry of a set change that re-tiers the tables (hd_keycarry.h):
+// row r of the snapshot keeps the key of its old slot in a stash of its own
+// -- the key and state arrays are freed with the tables -- when that slot's
+// state says the key is there.  Launched before the tables are freed.
+__global__ __launch_bounds__(256) void k_key_gather(const uint32_t* __restrict__ snap_slot, uint32_t n,
+                                                    const uint32_t* __restrict__ state, const ge* __restrict__ pub,
+                                                    uint32_t n_state, uint32_t f0, uint32_t f1,
+                                                    ge* __restrict__ stash_key, uint32_t* __restrict__ stash_flag) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += stride) {
+        const uint32_t slot = snap_slot[r];
+        bool has = false;
+        if (slot >= 1 && slot < n_state && !(slot >= f0 && slot < f1)) {
+            const uint32_t st = state[slot];
+            has = st == HD_FB_LEARNED || st == HD_FB_READY;
+        }
+        if (has) stash_key[r] = pub[slot];
+        stash_flag[r] = has ? 1u : 0u;
+    }
+}
+
+// Pair i = (snapshot row, new slot): the row's key into the new slot, state
+// LEARNED, for the table builder.  After the new slot arrays exist and their
+// states are reset; the context is quiesced and every slot appears in one
+// pair at most, so plain stores do.
+__global__ __launch_bounds__(256) void k_key_carry(const uint32_t* __restrict__ pairs, uint32_t n, uint32_t n_rows,
+                                                   const ge* __restrict__ stash_key,
+                                                   const uint32_t* __restrict__ stash_flag, uint32_t nslots,
+                                                   ge* __restrict__ pub, uint32_t* __restrict__ state) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const uint32_t row = pairs[2 * i], slot = pairs[2 * i + 1];
+        if (row >= n_rows || slot < 1 || slot >= nslots || !stash_flag[row]) continue;
+        pub[slot] = stash_key[row];
+        state[slot] = HD_FB_LEARNED;
+    }
+}
+
 namespace {
 uint32_t key_grid(const hd_ctx* ctx, uint32_t n) {
     return (uint32_t)std::min<uint64_t>(((uint64_t)n + 255u) / 256u, (uint64_t)std::max(ctx->n_cu, 1) * 8u);
 }
 }  // namespace
+
+int hd_key_stash_gather(hd_ctx* ctx, const uint32_t* snap_slot, uint32_t n, const FbKeyView& old, uint32_t f0,
+                        uint32_t f1, FbKeyStash* st) {
+    if (n == 0 || !old.state || !old.pub) return HD_OK;
+    // flag (n words), then the index words both kernels read: the n snapshot
+    // slots here, the (row, slot) pairs of a carry later (2 n at most)
+    KICHK(hipMalloc(&st->key, sizeof(ge) * (size_t)n), "key stash");
+    KICHK(hipMalloc(&st->words, 4 * 3 * (size_t)n), "key stash index");
+    st->n = n;
+    hipStream_t s = ctx->stream;
+    uint32_t* d_slot = st->words + n;
+    KICHK(hipMemcpyAsync(d_slot, snap_slot, 4 * (size_t)n, hipMemcpyHostToDevice, s), "key stash upload");
+    (void)hipGetLastError();
+    k_key_gather<<<key_grid(ctx, n), 256, 0, s>>>(d_slot, n, old.state, old.pub, old.nslots, f0, f1, st->key, st->words);
+    KICHK(hipGetLastError(), "k_key_gather launch");
+    KICHK(hipStreamSynchronize(s), "key stash gather");
+    return HD_OK;
+}
+
+int hd_key_stash_carry(hd_ctx* ctx, const FbKeyStash& st, const std::pair<uint32_t, uint32_t>* carry, uint32_t n,
+                       const FbKeyView& now) {
+    if (n == 0) return HD_OK;
+    if (!st.key || !st.words || n > st.n || !now.state || !now.pub) return HD_EINVAL;
+    std::vector<uint32_t> pairs(2 * (size_t)n);
+    for (uint32_t i = 0; i < n; i++) {
+        pairs[2 * i] = carry[i].first;
+        pairs[2 * i + 1] = carry[i].second;
+    }
+    hipStream_t s = ctx->stream;
+    uint32_t* d_pairs = st.words + st.n;
+    KICHK(hipMemcpyAsync(d_pairs, pairs.data(), 4 * pairs.size(), hipMemcpyHostToDevice, s), "key carry upload");
+    (void)hipGetLastError();
+    k_key_carry<<<key_grid(ctx, n), 256, 0, s>>>(d_pairs, n, st.n, st.key, st.words, now.nslots, now.pub, now.state);
+    KICHK(hipGetLastError(), "k_key_carry launch");
+    KICHK(hipStreamSynchronize(s), "key carry");   // (pairs is read until then)
+    return HD_OK;
+}
+
+void hd_key_stash_free(FbKeyStash* st) {
+    if (st->key) (void)hipFree(st->key);
+    if (st->words) (void)hipFree(st->words);
+    *st = FbKeyStash{};
+}
 
 extern "C" {
 

@@ -285,7 +285,10 @@ class Ingress:
         procsAllowed (the verifier's admitted set) and f.  keys: public keys
         (rows of 64 bytes, X || Y) imported after the set change
         (Verifier.import_keys: untrusted, each must hash to an admitted
-        signatory), so the first push authenticates against known keys."""
+        signatory), so the first push authenticates against known keys.  The
+        keys the verifier already knows of signatories that stay admitted are
+        kept by the set change itself (Verifier.set_signatories), so `keys` is
+        for a restart, a pubkey format change or signatories that are new."""
         if int(height) <= self.height:
             return False
         self.height = int(height)

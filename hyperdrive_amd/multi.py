@@ -18,7 +18,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import HDError
-from .verify import Batch, TallyResult, VerifyResult, Verifier, _as_rows, _ptr
+from .verify import Batch, TallyResult, VerifyResult, Verifier, _as_rows, _ptr, set_change_info
 
 
 class MultiVerifier:
@@ -60,9 +60,15 @@ class MultiVerifier:
         return bool(r.value)
 
     def set_signatories(self, signatories) -> None:
+        """hd_multi_set_signatories: Verifier.set_signatories on every context;
+        each keeps or carries its own known keys as described there."""
         arr = _as_rows(signatories, 32)
         self._check(self._lib.hd_multi_set_signatories(self._m, _ptr(arr), len(arr)), "hd_multi_set_signatories")
         self.n_signatories = len(arr)
+
+    def last_set_change(self, k: int = 0) -> dict:
+        """Verifier.last_set_change of context k."""
+        return set_change_info(self._lib, self._lib.hd_multi_ctx(self._m, k), self._check)
 
     def import_keys(self, keys) -> Tuple[np.ndarray, np.ndarray]:
         """hd_multi_import_keys: Verifier.import_keys on every context."""

@@ -53,6 +53,13 @@ def _ptr(a: Optional[np.ndarray]):
     return a.ctypes.data
 
 
+def set_change_info(lib, ctx, check) -> dict:
+    """hd_ctx_set_change_info of a context handle, as a dict of its fields"""
+    info = _lib.HdSetChangeInfo()
+    check(lib.hd_ctx_set_change_info(ctx, ctypes.byref(info)), "hd_ctx_set_change_info")
+    return {name: int(getattr(info, name)) for name, _ in info._fields_}
+
+
 @dataclass
 class Batch:
     """Structure-of-arrays batch in host memory (hd_batch)."""
@@ -584,9 +591,24 @@ class Verifier:
         return self._ctx
 
     def set_signatories(self, signatories) -> None:
+        """hd_set_signatories.  Known keys of signatories that stay admitted
+        are still known on return, also when the new set size makes the
+        context pick another key-table width (their tables are rebuilt inside
+        the call); a forced ``key_width`` that differs from the current one, a
+        pubkey format change and a set change that fails forget every key.
+        ``last_set_change()`` says what happened."""
         arr = _as_rows(signatories, 32)
         self._check(self._lib.hd_set_signatories(self._ctx, _ptr(arr), len(arr)), "hd_set_signatories")
         self.n_signatories = len(arr)
+
+    def last_set_change(self) -> dict:
+        """hd_ctx_set_change_info: what the last set_signatories did to the
+        known keys -- ``width_before`` / ``width_after`` (table widths in
+        bits), ``kept`` (left READY in place), ``carried`` (rebuilt at another
+        width or after a failed allocation), ``dropped`` (lost: the signatory
+        left the set, or no slot).  All zero before the first set change or
+        with the fast path off."""
+        return set_change_info(self._lib, self._ctx, self._check)
 
     def set_pubkey_format(self, fmt) -> None:
         """hd_ctx_set_pubkey_format (values as ``compressed`` of the

@@ -130,12 +130,36 @@ int hd_ctx_set_pubkey_format(hd_ctx* ctx, int format);
  * allowed.  Signer indices reported by the library index this array.
  * Blocking: waits for the context's device work in flight (a verify call
  * still learning keys must not see its slots reassigned), so call it between
- * batches, as ResetHeight does (replica/replica.go:136-144). */
+ * batches, as ResetHeight does (replica/replica.go:136-144).
+ * Known keys (fast path below): every key the context knows, learned or
+ * imported, of a signatory that stays admitted is still known on return,
+ * whatever the change does to the key tables.  At an unchanged table width
+ * its tables stay as they are.  When the new set size makes the context pick
+ * another width (narrower or wider), or a table allocation fails and the
+ * change retries at the next narrower width, the keys are carried over on the
+ * device and their tables are rebuilt at the new width inside this call: the
+ * next verify call finds them built.  A carried key that gets no slot at the
+ * new width (budget) is dropped.  Three exceptions, which forget every key:
+ * a forced width (HD_VAR_KEY_WIDTH != 0) that differs from the current one; a
+ * pubkey format change (hd_ctx_set_pubkey_format); and a set change that
+ * fails (HD_ENOMEM at every width).  The foreign-key block is emptied on
+ * every set change.  No output of a verify or authenticate call depends on
+ * any of this. */
 int hd_set_signatories(hd_ctx* ctx, const uint8_t* sigs32, uint32_t n);
+typedef struct {
+    int width_before, width_after;   /* table widths in bits */
+    uint32_t kept;      /* keys left READY in place, tables untouched */
+    uint32_t carried;   /* keys rebuilt at another width or after a failed allocation */
+    uint32_t dropped;   /* known keys lost: signatory left the set, or no slot */
+} hd_set_change_info;
+/* what the context's last hd_set_signatories did to its known keys;
+ * all zero before the first one or with the fast path off */
+int hd_ctx_set_change_info(hd_ctx* ctx, hd_set_change_info* out);
 /* Public keys of admitted signatories, supplied by the caller (a replica
  * holds its peers' keys, or exported them before it stopped), so that the
- * known-key fast path below does not start cold after a restart, a format
- * change or a set change.  The keys are not trusted: a signatory is SHA-256
+ * known-key fast path below does not start cold after a restart or a format
+ * change (a set change keeps the keys by itself, see hd_set_signatories).
+ * The keys are not trusted: a signatory is SHA-256
  * of its key's encoding, so each key is checked to lie on the curve, hashed
  * in the context's pubkey format and looked up in the admitted set; a key
  * that hashes to no admitted signatory is not stored.  An import changes no
@@ -143,9 +167,10 @@ int hd_set_signatories(hd_ctx* ctx, const uint8_t* sigs32, uint32_t n);
  * known before its first VALID message instead of after it.
  * Both calls wait for the context's device work in flight and are synchronous
  * (call them between batches, as hd_set_signatories).  Imported keys are kept
- * and dropped exactly as learned ones (kept across hd_set_signatories for
- * signatories that stay admitted; dropped by a pubkey format change and when
- * a set change picks another table width). */
+ * and dropped exactly as learned ones: kept across hd_set_signatories for
+ * signatories that stay admitted, a change of table width included; dropped
+ * by a pubkey format change, by a set change to another forced width
+ * (HD_VAR_KEY_WIDTH) and by a set change that fails. */
 #define HD_KEY_IMPORTED     0  /* slot was empty: key stored, tables built               */
 #define HD_KEY_KNOWN        1  /* slot already had a key (necessarily this one)          */
 #define HD_KEY_NOT_ADMITTED 2  /* SHA-256(encoding) is not in the admitted set           */
@@ -165,7 +190,9 @@ int hd_import_keys(hd_ctx* ctx, const uint8_t* keys64, uint32_t n, uint8_t* stat
  * (duplicates included): known[i] = 1 and keys64[64 i ..] = X || Y when that
  * signatory's slot holds a key (learned or imported), else 0 and 64 zero
  * bytes.  *n_out = n_adm.  cap < n_adm: HD_ECAP with *n_out = n_adm, nothing
- * written. */
+ * written.  Right after a set change it reports the keys that change kept or
+ * carried (hd_set_signatories); nothing known after one of its three
+ * exceptions: another forced width, a format change, a failed mapping. */
 int hd_export_keys(hd_ctx* ctx, uint8_t* keys64, uint8_t* known, uint32_t cap, uint32_t* n_out);
 /* Known-key fast path (on by default; HD_VERIFY_FASTPATH=0 in the
  * environment turns it off for new contexts).  The first message of an
@@ -175,7 +202,8 @@ int hd_export_keys(hd_ctx* ctx, uint8_t* keys64, uint8_t* known, uint32_t cap, u
  * (R == s^-1 (m G + r P)) and only fall back to the full recovery when the
  * check fails.  Verdicts, recovered signatories, signer indices and bitmaps
  * are identical either way.  Keys are kept across hd_set_signatories for
- * signatories that stay admitted and dropped when the pubkey format changes. */
+ * signatories that stay admitted (a change of table width included; the
+ * exceptions are listed there) and dropped when the pubkey format changes. */
 int hd_ctx_set_fastpath(hd_ctx* ctx, int enable);
 /* known_keys: admitted signatories whose key tables are built;
  * last_fallback: messages of the last verify call that took the full
@@ -685,6 +713,10 @@ int hd_multi_destroy(hd_multi* m);
 int hd_multi_size(hd_multi* m, int* ngpus, int* uses_rccl);
 /* the context of device slot k (fast-path stats etc.), NULL if out of range */
 hd_ctx* hd_multi_ctx(hd_multi* m, int k);
+/* hd_set_signatories on every context: each keeps or carries its own known
+ * keys as that call states, with the same three exceptions (another forced
+ * width, a format change, a failed mapping); hd_ctx_set_change_info of
+ * hd_multi_ctx(m, k) says what context k did. */
 int hd_multi_set_signatories(hd_multi* m, const uint8_t* sigs32, uint32_t n);
 int hd_multi_set_pubkey_format(hd_multi* m, int format);
 /* hd_import_keys on every context; HD_EDEVICE when the contexts disagree on a
