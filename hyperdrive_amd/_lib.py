@@ -141,6 +141,20 @@ class HdEvidenceOut(ctypes.Structure):
     _fields_ = [("offender", HdLogRows), ("against", HdLogRows)]
 
 
+class HdMqPropose(ctypes.Structure):
+    """include/hd_mq.h hd_mq_propose: one delivered propose (96 bytes)."""
+    _fields_ = [("index", ctypes.c_uint32), ("sender", ctypes.c_int32), ("height", ctypes.c_int64),
+                ("round", ctypes.c_int64), ("valid_round", ctypes.c_int64), ("value32", ctypes.c_uint8 * 32),
+                ("from32", ctypes.c_uint8 * 32)]
+
+
+class HdMqTaken(ctypes.Structure):
+    """include/hd_mq.h hd_mq_taken (hd_mq_consume_device)."""
+    _fields_ = [("n", ctypes.c_uint32), ("removed", ctypes.c_uint32), ("batch", HdBatch),
+                ("d_sender", ctypes.c_void_p), ("d_valid_bitmap", ctypes.c_void_p), ("d_value_ok", ctypes.c_void_p),
+                ("n_proposes", ctypes.c_uint32), ("proposes", ctypes.c_void_p)]
+
+
 class HdTallyTicket(ctypes.Structure):
     """include/hd_verify.h hd_tally_ticket (hd_tally_device_bitmap_async / hd_tally_collect)."""
     _fields_ = [("stage", ctypes.c_void_p), ("stage_cap", ctypes.c_size_t), ("dup", ctypes.c_int),
@@ -326,6 +340,11 @@ SIGNATURES = {
                                            ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p, ctypes.c_void_p,
                                            ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]),
     "hd_mq_drop_below": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64]),
+    "hd_mq_consume_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_uint32,
+                                            ctypes.POINTER(HdMqTaken)]),
+    "hd_mq_taken_value_ok": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32]),
+    "hd_mq_taken_read": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32,
+                                        ctypes.POINTER(HdBatchOut), ctypes.c_void_p]),
     # include/hd_digest.h
     "hd_digest_batch_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(HdBatch),
                                               ctypes.c_void_p, ctypes.c_void_p]),

@@ -39,6 +39,7 @@
 #include "../../include/hd_mq.h"
 #include "../../include/hd_votes.h"
 #include "hd_internal.h"
+#include "hd_mqtake.h"
 
 using namespace hd;
 
@@ -539,6 +540,160 @@ __global__ void k_mq_commit(uint32_t nsend, const uint32_t* __restrict__ newhead
     for (uint32_t s = blockIdx.x * blockDim.x + threadIdx.x; s < nsend; s += gridDim.x * blockDim.x) head[s] = newhead[s];
 }
 
+// ---- consume into device memory (hd_mq_consume_device) ----------------------
+// The signature rows of a block's 256 destination rows k0 .. k0 + 255 of dsig
+// (rows at or past n are not written), as k_mq_gather moves them but with no
+// byte access to global memory: lane tid stages the 17 aligned dwords that
+// cover its source row sg (nullptr: zeros) in LDS -- up to 3 bytes on either
+// side of the row are read with them, inside the pool's allocation (the sig
+// array starts 8-byte aligned and the sender array follows it) -- and the
+// block writes its contiguous, 4-byte aligned range as whole dwords assembled
+// from LDS bytes.  The last block's final dword is padded with zeros: the
+// destination has a spare row (taken_reserve), so it stays inside the array.
+__device__ __forceinline__ void mq_sig_block(const uint8_t* sg, uint32_t tid, uint32_t k0, uint32_t n,
+                                             uint8_t* __restrict__ dsig, uint32_t* rows_lds, uint8_t* off_lds) {
+    uint32_t* my = rows_lds + 17 * tid;
+    uint32_t off = 0;
+    if (sg) {
+        off = (uint32_t)((uintptr_t)sg & 3u);
+        const uint32_t* w32 = reinterpret_cast<const uint32_t*>(sg - off);
+        for (int j = 0; j < 17; j++) my[j] = w32[j];
+    } else {
+        for (int j = 0; j < 17; j++) my[j] = 0;
+    }
+    off_lds[tid] = (uint8_t)off;
+    __syncthreads();
+    if (k0 >= n) return;
+    const uint32_t nb = n - k0 < 256u ? n - k0 : 256u;
+    const uint32_t bytes = 65u * nb, words = (bytes + 3u) >> 2;
+    const uint8_t* lb = reinterpret_cast<const uint8_t*>(rows_lds);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(dsig + 65 * (size_t)k0);
+    for (uint32_t D = tid; D < words; D += 256u) {
+        uint32_t v = 0;
+        for (uint32_t t = 0; t < 4; t++) {
+            const uint32_t b = 4 * D + t;
+            if (b < bytes) {
+                const uint32_t row = b / 65u, col = b - 65u * row;
+                v |= (uint32_t)lb[68 * row + off_lds[row] + col] << (8 * t);
+            }
+        }
+        dst[D] = v;
+    }
+}
+
+// fields of pool entry e other than the signature -> row k of d
+__device__ __forceinline__ void mq_row_copy(const Pool& p, uint32_t e, const Pool& d, uint32_t k) {
+    d.sender[k] = p.sender[e];
+    d.h[k] = p.h[e];
+    d.r[k] = p.r[e];
+    d.vr[k] = p.vr[e];
+    for (int w = 0; w < 2; w++) {
+        reinterpret_cast<uint4*>(d.value + 32 * (size_t)k)[w] = reinterpret_cast<const uint4*>(p.value + 32 * (size_t)e)[w];
+        reinterpret_cast<uint4*>(d.from + 32 * (size_t)k)[w] = reinterpret_cast<const uint4*>(p.from + 32 * (size_t)e)[w];
+    }
+}
+
+// The delivery of a planned consume, one delivered row per lane (k_mq_take
+// runs one block per sender: 100 blocks for C2's 100 x 1,000 rows).  Row k
+// finds its sender in the plan's offsets (hd_mqtake.h) and takes entry
+// head[s] + (k - off[s]) of the pool, head being the heads before the commit.
+// The same launch writes value_ok[k] = 1, the valid bitmap (one ballot per
+// wavefront gives two words, as k_fast_cmp's) and the propose flag the select
+// of the propose rows reads.
+__global__ __launch_bounds__(256) void k_mq_take_rows(Pool p, const uint32_t* __restrict__ head,
+                                                      const uint32_t* __restrict__ off, uint32_t ns, uint32_t n,
+                                                      Pool d, uint8_t* __restrict__ value_ok,
+                                                      uint32_t* __restrict__ bitmap, uint8_t* __restrict__ is_propose) {
+    __shared__ uint32_t rows_lds[256 * 17];
+    __shared__ uint8_t off_lds[256];
+    const uint32_t tid = threadIdx.x, k0 = blockIdx.x * 256u, k = k0 + tid;
+    const uint8_t* sg = nullptr;
+    if (k < n) {
+        const uint32_t s = hd::mq_take_locate(off, ns, k);
+        const uint32_t e = head[s] + (k - off[s]);
+        mq_row_copy(p, e, d, k);
+        const uint8_t t = p.type[e];
+        d.type[k] = t;
+        value_ok[k] = 1;
+        is_propose[k] = t == HD_TYPE_PROPOSE;
+        sg = p.sig + 65 * (size_t)e;
+    }
+    const unsigned long long in = __ballot(k < n);
+    const uint32_t lane = tid & 63u, i0 = k - lane;   // multiple of 64
+    if (lane == 0 && i0 < n) {
+        bitmap[i0 >> 5] = (uint32_t)in;
+        if (i0 + 32 < n) bitmap[(i0 >> 5) + 1] = (uint32_t)(in >> 32);
+    }
+    mq_sig_block(sg, tid, k0, n, d.sig, rows_lds, off_lds);
+}
+
+// The delivered proposes (pidx: their rows, in order; *count of them) packed
+// as hd_mq_propose into the mapped host block: header {count, -, seq} in 64
+// bytes, then up to `room` rows.  The host spins on the sequence word, written
+// last by the block that finishes last; a count above `room` makes it grow
+// the block and pack again.
+#define HD_MQ_PROP_HDR 64
+__global__ __launch_bounds__(256) void k_mq_pack_proposes(Pool t, const uint32_t* __restrict__ pidx,
+                                                          const uint32_t* __restrict__ count, uint32_t room,
+                                                          uint8_t* __restrict__ block, uint32_t* __restrict__ done,
+                                                          uint32_t seq) {
+    const uint32_t np = *count, m = np < room ? np : room;
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j < m) {
+        const uint32_t k = pidx[j];
+        uint32_t* o = reinterpret_cast<uint32_t*>(block + HD_MQ_PROP_HDR + 96 * (size_t)j);
+        const uint64_t hv = (uint64_t)t.h[k], rv = (uint64_t)t.r[k], vv = (uint64_t)t.vr[k];
+        o[0] = k;
+        o[1] = (uint32_t)t.sender[k];
+        o[2] = (uint32_t)hv;
+        o[3] = (uint32_t)(hv >> 32);
+        o[4] = (uint32_t)rv;
+        o[5] = (uint32_t)(rv >> 32);
+        o[6] = (uint32_t)vv;
+        o[7] = (uint32_t)(vv >> 32);
+        const uint32_t* val = reinterpret_cast<const uint32_t*>(t.value + 32 * (size_t)k);
+        const uint32_t* frm = reinterpret_cast<const uint32_t*>(t.from + 32 * (size_t)k);
+        for (int w = 0; w < 8; w++) o[8 + w] = val[w];
+        for (int w = 0; w < 8; w++) o[16 + w] = frm[w];
+    }
+    __threadfence_system();
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        // *done counts the blocks that have written their rows (zero before
+        // the launch, zero again after it)
+        if (atomicAdd(done, 1u) + 1u == gridDim.x) {
+            *done = 0;
+            reinterpret_cast<uint32_t*>(block)[0] = np;
+            __threadfence_system();
+            __hip_atomic_store(reinterpret_cast<uint32_t*>(block) + 2, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
+
+// hd_mq_taken_value_ok: value_ok[pidx[j]] = ok[j]
+__global__ void k_mq_value_ok(uint32_t np, const uint8_t* __restrict__ ok, const uint32_t* __restrict__ pidx,
+                              uint8_t* __restrict__ value_ok) {
+    const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < np) value_ok[pidx[j]] = ok[j];
+}
+
+// hd_mq_taken_read: row k of d := row idx[k] (idx NULL: first + k) of the
+// delivery t, one row per lane
+__global__ __launch_bounds__(256) void k_mq_taken_gather(Pool t, const uint32_t* __restrict__ idx, uint32_t first,
+                                                         uint32_t n, Pool d) {
+    __shared__ uint32_t rows_lds[256 * 17];
+    __shared__ uint8_t off_lds[256];
+    const uint32_t tid = threadIdx.x, k0 = blockIdx.x * 256u, k = k0 + tid;
+    const uint8_t* sg = nullptr;
+    if (k < n) {
+        const uint32_t e = idx ? idx[k] : first + k;
+        mq_row_copy(t, e, d, k);
+        d.type[k] = t.type[e];
+        sg = t.sig + 65 * (size_t)e;
+    }
+    mq_sig_block(sg, tid, k0, n, d.sig, rows_lds, off_lds);
+}
+
 // A consume in one launch, for queues of at most 1024 senders (the usual
 // case: one queue per validator): procsAllowed flags in LDS (the dict looked
 // up for each allowed signatory), the plan (k_mq_plan's cut per sender and the
@@ -858,7 +1013,7 @@ int bits_of(uint64_t range) {
 
 enum MqSlot { MQ_FLAG, MQ_NEWIDX, MQ_NSEL, MQ_HK, MQ_RK, MQ_SK, MQ_PERM0, MQ_PERM1, MQ_K64A, MQ_K64B, MQ_K32A, MQ_K32B,
               MQ_HEAD, MQ_KEEP, MQ_SEL, MQ_RED, MQ_TMP, MQ_SID, MQ_LSLOT, MQ_LCLAIM, MQ_LID, MQ_REPS, MQ_ALLOW,
-              MQ_LIST, MQ_DELIV, MQ_SEL2, MQ_HEADS, MQ_SEND, MQ_NEWHEAD, MQ_OFF, MQ_TOT, MQ_STAGE, MQ_WIN, MQ_SELCNT, MQ__N };
+              MQ_LIST, MQ_DELIV, MQ_SEL2, MQ_HEADS, MQ_SEND, MQ_NEWHEAD, MQ_OFF, MQ_TOT, MQ_STAGE, MQ_WIN, MQ_SELCNT, MQ_TKSTAGE, MQ_TKIDX, MQ__N };
 
 struct hd_mq {
     hd_ctx* ctx = nullptr;
@@ -913,6 +1068,29 @@ struct hd_mq {
     const uint8_t* pf_base = nullptr;     // first window row in the stage
     std::vector<uint32_t> pf_start;       // rows of height pf_dev + 1 + j: pf_idx[pf_start[j] .. pf_start[j + 1])
     std::vector<uint32_t> pf_idx;
+    // hd_mq_consume_device: the delivery, a Pool-shaped region of its own
+    // (not MQ_STAGE, which the host consume reuses) with value_ok, the valid
+    // bitmap, the propose rows' indices and the pack kernel's block counter
+    // behind it; and the mapped host block of the propose rows (64-byte
+    // header {count, -, sequence word}, then the rows)
+    Pool taken;                    // taken.n = rows delivered
+    uint8_t* tk_vok = nullptr;
+    uint32_t* tk_bitmap = nullptr;
+    uint32_t* tk_pidx = nullptr;
+    uint32_t* tk_done = nullptr;
+    bool tk_live = false;          // a delivery stands: ended by the next insert, consume or drop
+    uint32_t tk_np = 0;            // its propose rows
+    uint8_t* tk_prop = nullptr;
+    uint8_t* tk_prop_dev = nullptr;
+    uint32_t tk_prop_room = 0;     // rows the block holds
+    uint32_t tk_seq = 0;
+    // hd_mq_taken_value_ok: mapped staging of the caller's bytes; the event
+    // marks the scatter that last read them
+    uint8_t* tk_ok = nullptr;
+    uint8_t* tk_ok_dev = nullptr;
+    size_t tk_ok_cap = 0;
+    hipEvent_t tk_ok_ev = nullptr;
+    bool tk_ok_pending = false;
 };
 
 #define QCHK(expr, what)                                           \
@@ -1408,6 +1586,10 @@ int hd_mq_destroy(hd_mq* q) {
     if (q->hstage) (void)hipHostFree(q->hstage);
     if (q->mstage) (void)hipHostFree(q->mstage);
     if (q->rep) (void)hipHostFree(q->rep);
+    if (q->taken.base) (void)hipFree(q->taken.base);
+    if (q->tk_prop) (void)hipHostFree(q->tk_prop);
+    if (q->tk_ok) (void)hipHostFree(q->tk_ok);
+    if (q->tk_ok_ev) (void)hipEventDestroy(q->tk_ok_ev);
     if (q->order_ev) (void)hipEventDestroy(q->order_ev);
     delete q;
     return HD_OK;
@@ -1428,6 +1610,7 @@ int hd_mq_senders(hd_mq* q, uint32_t* n) {
 int hd_mq_insert_device(hd_mq* q, const hd_batch* d_batch, const uint8_t* d_insert, void* stream) {
     if (!q || !d_batch) return HD_EINVAL;
     if (q->failed) return mq_refuse(q);
+    q->tk_live = false;   // ends a delivery of hd_mq_consume_device
     const uint32_t nb = d_batch->n;
     if (nb == 0) return HD_OK;  // empty device tensors may have NULL data pointers
     if (!d_batch->type || !d_batch->height || !d_batch->round || !d_batch->value32 || !d_batch->from32)
@@ -1451,6 +1634,7 @@ int hd_mq_insert_verified_device(hd_mq* q, const hd_batch* d_batch, const uint8_
                                  void* stream) {
     if (!q || !d_batch) return HD_EINVAL;
     if (q->failed) return mq_refuse(q);
+    q->tk_live = false;   // ends a delivery of hd_mq_consume_device
     const uint32_t nb = d_batch->n;
     if (nb == 0) return HD_OK;
     if (!d_verdict) return HD_EINVAL;
@@ -1717,6 +1901,7 @@ int hd_mq_consume(hd_mq* q, int64_t h, const uint8_t* allowed32, uint32_t n_allo
                   int32_t* out_sender, uint32_t cap, uint32_t* n_out, uint32_t* n_removed) {
     if (!q || !out || !n_out) return HD_EINVAL;
     if (q->failed) return mq_refuse(q);
+    q->tk_live = false;   // ends a delivery of hd_mq_consume_device
     if (!out->type || !out->height || !out->round || !out->value32 || !out->from32) return HD_EINVAL;
     if (allowed32 == nullptr && n_allowed != 0) return HD_EINVAL;
     *n_out = 0;
@@ -1833,6 +2018,7 @@ int hd_mq_consume_votes(hd_mq* q, struct hd_votes* v, int64_t h, const uint8_t* 
 int hd_mq_drop_below(hd_mq* q, int64_t h) {
     if (!q) return HD_EINVAL;
     if (q->failed) return mq_refuse(q);
+    q->tk_live = false;   // ends a delivery of hd_mq_consume_device
     if (q->pf) {
         if (h - 1 <= q->pf_done) return HD_OK;   // nothing below h is left
         if (h - 1 <= q->pf_max) {                // the window's heights (pf_done, h - 1] leave undelivered
@@ -1852,6 +2038,254 @@ int hd_mq_drop_below(hd_mq* q, int64_t h) {
     int rc = mq_plan(q, h, 1, nullptr, tot, s);
     if (rc) return rc;
     return mq_commit(q, tot[1], s);
+}
+
+// ---- consume into device memory ---------------------------------------------
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// The delivery's region for n rows: one row more than n, so that the dword
+// that ends the last signature row stays inside the sig array (mq_sig_block).
+static int taken_reserve(hd_mq* q, uint32_t n) {
+    const uint32_t need = (n + 16u) & ~15u;
+    Pool& t = q->taken;
+    if (need > t.cap) {
+        const uint32_t cap = (std::max(need, std::max(1024u, t.cap + t.cap / 2)) + 15u) & ~15u;
+        const size_t c = cap, o_vok = pool_bytes(cap), o_bm = o_vok + c, o_pidx = o_bm + up16(4 * (c / 32 + 2)),
+                     o_done = o_pidx + 4 * c, bytes = o_done + 64;
+        void* base = nullptr;
+        hipError_t e = hipMalloc(&base, bytes);
+        if (e != hipSuccess) return hd_ctx_fail(q->ctx, e, "hipMalloc mq delivery");
+        if (t.base) (void)hipFree(t.base);
+        t = pool_view(base, cap);
+        char* b = (char*)base;
+        q->tk_vok = (uint8_t*)(b + o_vok);
+        q->tk_bitmap = (uint32_t*)(b + o_bm);
+        q->tk_pidx = (uint32_t*)(b + o_pidx);
+        q->tk_done = (uint32_t*)(b + o_done);
+        QCHK(hipMemsetAsync(q->tk_done, 0, 64, q->ctx->stream), "clear mq delivery counter");
+    }
+    return HD_OK;
+}
+
+// the mapped block of the propose rows, for `room` of them
+static int taken_prop_reserve(hd_mq* q, uint32_t room) {
+    if (room <= q->tk_prop_room) return HD_OK;
+    if (q->tk_prop) (void)hipHostFree(q->tk_prop);
+    q->tk_prop = nullptr;
+    q->tk_prop_room = 0;
+    room = std::max(room + room / 2, 1024u);
+    void* h = nullptr;
+    QCHK(hipHostMalloc(&h, HD_MQ_PROP_HDR + sizeof(hd_mq_propose) * (size_t)room,
+                       hipHostMallocMapped | hipHostMallocCoherent), "mq propose block");
+    q->tk_prop = (uint8_t*)h;
+    void* d = nullptr;
+    QCHK(hipHostGetDevicePointer(&d, h, 0), "mq propose block pointer");
+    q->tk_prop_dev = (uint8_t*)d;
+    q->tk_prop_room = room;
+    memset(h, 0, HD_MQ_PROP_HDR);
+    return HD_OK;
+}
+
+// Pack the propose rows (count on the device) and wait for the block: the
+// sequence word is written after every row, so everything queued on the
+// stream before the pack has completed too.  Past ~0.2 s the stream is
+// synchronised (a fault surfaces there).
+static int taken_pack(hd_mq* q, uint32_t n, const uint32_t* count_dev, hipStream_t s, uint32_t* np) {
+    const uint32_t seq = ++q->tk_seq ? q->tk_seq : ++q->tk_seq;   // never 0
+    const uint32_t room = q->tk_prop_room;
+    k_mq_pack_proposes<<<nblk(std::max(std::min(room, n), 1u)), 256, 0, s>>>(q->taken, q->tk_pidx, count_dev, room,
+                                                                          q->tk_prop_dev, q->tk_done, seq);
+    QCHK(hipGetLastError(), "k_mq_pack_proposes");
+    volatile uint32_t* word = (volatile uint32_t*)q->tk_prop + 2;
+    const auto t0 = std::chrono::steady_clock::now();
+    while (*word != seq) {
+        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
+            QCHK(hipStreamSynchronize(s), "consume_device sync");
+            if (*word != seq) return hd_ctx_fail(q->ctx, hipErrorUnknown, "consume_device signal");
+            break;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    *np = ((volatile uint32_t*)q->tk_prop)[0];
+    return HD_OK;
+}
+
+static void taken_view(const hd_mq* q, uint32_t removed, hd_mq_taken* out) {
+    const Pool& t = q->taken;
+    out->n = t.n;
+    out->removed = removed;
+    out->n_proposes = q->tk_np;
+    if (t.n == 0) return;
+    out->batch = hd_batch{t.n, t.type, t.h, t.r, t.vr, t.value, t.from, t.sig};
+    out->d_sender = t.sender;
+    out->d_valid_bitmap = q->tk_bitmap;
+    out->d_value_ok = q->tk_vok;
+    out->proposes = (const hd_mq_propose*)(q->tk_prop + HD_MQ_PROP_HDR);
+}
+
+int hd_mq_consume_device(hd_mq* q, int64_t h, const uint8_t* allowed32, uint32_t n_allowed, hd_mq_taken* out) {
+    static_assert(sizeof(hd_mq_propose) == 96, "hd_mq_propose is 96 bytes");
+    if (!q || !out) return HD_EINVAL;
+    if (q->failed) return mq_refuse(q);
+    if (allowed32 == nullptr && n_allowed != 0) return HD_EINVAL;
+    memset(out, 0, sizeof *out);
+    q->tk_live = false;
+    (void)hipSetDevice(q->ctx->device);
+    int rc = pf_sync(q);   // a staged window is committed first
+    if (rc) return rc;
+    hipStream_t s = q->ctx->stream;
+    q->taken.n = 0;
+    q->tk_np = 0;
+    if (q->live == 0) {
+        q->tk_live = true;
+        return HD_OK;
+    }
+    // 1. procsAllowed -> allow[sender]
+    const uint32_t ns = q->nsend;
+    const uint32_t* list = q->ctx->d_adm;   // the ctx's admitted set now (sorted, big-endian words)
+    uint32_t na = q->ctx->n_adm;
+    int be = 1;
+    if (allowed32) {
+        na = n_allowed;
+        be = 0;
+        list = nullptr;
+        if (na) {
+            uint32_t* d = (uint32_t*)qbuf(q, MQ_LIST, 32 * (size_t)na, &rc);
+            if (rc) return rc;
+            QCHK(hipMemcpyAsync(d, allowed32, 32 * (size_t)na, hipMemcpyHostToDevice, s), "allowed upload");
+            list = d;
+        }
+    }
+    uint8_t* allow = (uint8_t*)qbuf(q, MQ_ALLOW, ns, &rc);
+    if (rc) return rc;
+    QCHK(hipMemsetAsync(allow, 0, ns, s), "clear allow");
+    if (na) k_mq_allow<<<nblk(na), 256, 0, s>>>(na, list, be, dict_of(q), allow);
+    QCHK(hipGetLastError(), "k_mq_allow");
+    // 2. the plan and its totals
+    uint32_t tot[2];
+    if ((rc = mq_plan(q, h, 0, allow, tot, s))) return rc;
+    const uint32_t n = tot[0], removed = tot[1];
+    if (n == 0) {   // nothing delivered: the removed prefixes still leave
+        if ((rc = mq_commit(q, removed, s))) return rc;
+        QCHK(hipStreamSynchronize(s), "consume_device commit");
+        q->tk_live = true;
+        out->removed = removed;
+        return HD_OK;
+    }
+    // 3. every allocation, before anything is removed (mq_plan's wait covered
+    // a scatter into the previous delivery's value_ok: same stream)
+    q->tk_ok_pending = false;
+    if ((rc = taken_reserve(q, n))) return rc;
+    if ((rc = taken_prop_reserve(q, 1))) return rc;
+    uint8_t* flag = (uint8_t*)qbuf(q, MQ_FLAG, n, &rc);
+    if (rc) return rc;
+    // 4. the delivery, its propose rows' indices, the heads
+    k_mq_take_rows<<<nblk(n), 256, 0, s>>>(q->pool, (const uint32_t*)q->buf[MQ_HEADS].p,
+                                           (const uint32_t*)q->buf[MQ_OFF].p, ns, n, q->taken, q->tk_vok,
+                                           q->tk_bitmap, flag);
+    QCHK(hipGetLastError(), "k_mq_take_rows");
+    uint32_t* count_dev = nullptr;
+    if ((rc = select_idx(q, flag, n, q->tk_pidx, nullptr, s, 4, false, &count_dev))) return rc;
+    if ((rc = mq_commit(q, removed, s))) return rc;
+    // 5. the propose rows on the host; the wait covers the whole call
+    uint32_t np = 0;
+    if ((rc = taken_pack(q, n, count_dev, s, &np))) return rc;
+    if (np > q->tk_prop_room) {
+        if ((rc = taken_prop_reserve(q, np))) return rc;
+        if ((rc = taken_pack(q, n, count_dev, s, &np))) return rc;
+    }
+    q->taken.n = n;
+    q->tk_np = np;
+    q->tk_live = true;
+    taken_view(q, removed, out);
+    return HD_OK;
+}
+
+int hd_mq_taken_value_ok(hd_mq* q, const uint8_t* propose_ok, uint32_t n_proposes) {
+    if (!q) return HD_EINVAL;
+    if (q->failed) return mq_refuse(q);
+    if (!q->tk_live || n_proposes != q->tk_np) return HD_EINVAL;
+    if (n_proposes == 0) return HD_OK;
+    if (!propose_ok) return HD_EINVAL;
+    (void)hipSetDevice(q->ctx->device);
+    hipStream_t s = q->ctx->stream;
+    if (q->tk_ok_pending) {   // the staging bytes are still being read
+        QCHK(hipEventSynchronize(q->tk_ok_ev), "value_ok wait");
+        q->tk_ok_pending = false;
+    }
+    if (q->tk_ok_cap < n_proposes) {
+        if (q->tk_ok) (void)hipHostFree(q->tk_ok);
+        q->tk_ok = nullptr;
+        q->tk_ok_cap = 0;
+        const size_t want = std::max<size_t>(2 * (size_t)n_proposes, 4096);
+        void* hp = nullptr;
+        QCHK(hipHostMalloc(&hp, want, hipHostMallocMapped | hipHostMallocCoherent), "mq value_ok staging");
+        q->tk_ok = (uint8_t*)hp;
+        void* d = nullptr;
+        QCHK(hipHostGetDevicePointer(&d, hp, 0), "mq value_ok staging pointer");
+        q->tk_ok_dev = (uint8_t*)d;
+        q->tk_ok_cap = want;
+    }
+    if (!q->tk_ok_ev) QCHK(hipEventCreateWithFlags(&q->tk_ok_ev, hipEventDisableTiming), "mq value_ok event");
+    memcpy(q->tk_ok, propose_ok, n_proposes);
+    k_mq_value_ok<<<nblk(n_proposes), 256, 0, s>>>(n_proposes, q->tk_ok_dev, q->tk_pidx, q->tk_vok);
+    QCHK(hipGetLastError(), "k_mq_value_ok");
+    QCHK(hipEventRecord(q->tk_ok_ev, s), "mq value_ok record");
+    q->tk_ok_pending = true;
+    return HD_OK;
+}
+
+int hd_mq_taken_read(hd_mq* q, const uint32_t* idx, uint32_t first, uint32_t n, const hd_batch_out* out,
+                     int32_t* out_sender) {
+    if (!q || !out) return HD_EINVAL;
+    if (q->failed) return mq_refuse(q);
+    if (!out->type || !out->height || !out->round || !out->value32 || !out->from32) return HD_EINVAL;
+    if (!q->tk_live) return HD_EINVAL;
+    const uint32_t N = q->taken.n;
+    if (idx) {
+        for (uint32_t k = 0; k < n; k++)
+            if (idx[k] >= N) return HD_EINVAL;
+    } else if (first > N || n > N - first) {
+        return HD_EINVAL;
+    }
+    if (n == 0) return HD_OK;
+    (void)hipSetDevice(q->ctx->device);
+    hipStream_t s = q->ctx->stream;
+    int rc = 0;
+    const uint32_t r16 = (n + 16u) & ~15u;   // a spare row, as the delivery's region
+    const size_t bytes = pool_bytes(r16);
+    void* dst = qbuf(q, MQ_TKSTAGE, bytes, &rc);
+    if (rc) return rc;
+    uint32_t* didx = nullptr;
+    if (idx) {
+        didx = (uint32_t*)qbuf(q, MQ_TKIDX, 4 * (size_t)n, &rc);
+        if (rc) return rc;
+        QCHK(hipMemcpyAsync(didx, idx, 4 * (size_t)n, hipMemcpyHostToDevice, s), "read index upload");
+    }
+    if (q->hstage_cap < bytes) {
+        if (q->hstage) (void)hipHostFree(q->hstage);
+        q->hstage = nullptr;
+        q->hstage_cap = 0;
+        const size_t want = std::max(bytes + bytes / 2, (size_t)1 << 16);
+        QCHK(hipHostMalloc(&q->hstage, want, hipHostMallocDefault), "mq host stage");
+        q->hstage_cap = want;
+    }
+    const Pool d = pool_view(dst, r16);
+    k_mq_taken_gather<<<nblk(n), 256, 0, s>>>(q->taken, didx, first, n, d);
+    QCHK(hipGetLastError(), "k_mq_taken_gather");
+    QCHK(hipMemcpyAsync(q->hstage, dst, bytes, hipMemcpyDeviceToHost, s), "read download");
+    QCHK(hipStreamSynchronize(s), "read sync");
+    const Pool hp = pool_view(q->hstage, r16);
+    struct Cp { void* dst; const void* src; size_t sz; } cp[] = {
+        {out->type, hp.type, (size_t)n},          {out->height, hp.h, 8 * (size_t)n},
+        {out->round, hp.r, 8 * (size_t)n},        {out->valid_round, hp.vr, 8 * (size_t)n},
+        {out->value32, hp.value, 32 * (size_t)n}, {out->from32, hp.from, 32 * (size_t)n},
+        {out->sig65, hp.sig, 65 * (size_t)n},     {out_sender, hp.sender, 4 * (size_t)n},
+    };
+    for (auto& x : cp)
+        if (x.dst) memcpy(x.dst, x.src, x.sz);
+    if (out->adv_class) memset(out->adv_class, 0, n);
+    return HD_OK;
 }
 
 }  // extern "C"

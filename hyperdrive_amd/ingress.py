@@ -16,6 +16,7 @@ for a whole batch:
     res.events                              # HD_VOTE_EV_* quorum crossings per delivered vote (f known)
     ing.open_log(schedule)                  # a device log of the height (hd_log): proposes included
     res, dec = ing.flush_decide()           # flush() + the rules the consumed messages fired (dec.new_firings)
+    taken, dec = ing.flush_decide_device()  # the same insert with the delivery kept on the device (mq.Taken)
     ing.advance_height(h + 1)               # the Process committed: CurrentHeight++, logs emptied (process.go:710-725)
     ing.reset_height(h + 5, signatories)    # ResetHeight: ignored unless above the current height
                                             # (replica.go:222-225); logs emptied, mq.DropMessagesBelowHeight,
@@ -258,6 +259,34 @@ class Ingress:
         b = res.consumed
         vok = value_ok(b) if callable(value_ok) else value_ok
         return res, self.log.insert(b, np.zeros(len(b), np.uint8), vok, catch=catch, evidence=evidence)
+
+    def flush_decide_device(self, value_ok=None, catch=False, evidence=False):
+        """flush_decide() without the batch's round trip through the host:
+        ``mq.consume_device(height)`` leaves the delivery on the device
+        (mq.Taken) and the open log inserts it from there
+        (DecideLog.insert_device over ``taken.batch``, its bitmap and its
+        value_ok bytes).  Only the delivered proposes come to the host, for
+        validator.Valid: value_ok is None (every non-nil value is valid), one
+        byte per delivered PROPOSE (``taken.proposes``, delivery order), or a
+        callable that takes ``taken.proposes`` and returns those bytes.
+        catch, evidence: as flush_decide.  The host vote table ``self.votes``
+        is NOT fed: the firings, catch records and evidence rows of the log
+        take its place, and a caller that wants hd_votes keeps flush().
+        Both paths are launch-bound on a small flush and this one plans with
+        a round trip of its own, so flush_decide stays the default there
+        (DESIGN.md §5); this one is for the large deliveries, and for a host
+        that does not hold the batch.  The Taken is valid until the next call
+        on the queue.  Returns (Taken, LogInsertResult)."""
+        if self.log is None:
+            raise RuntimeError("flush_decide_device without open_log")
+        mq = self.mq
+        taken = mq.consume_device(self.height)
+        self._clean = (self.height, mq.inserts)
+        vok = value_ok(taken.proposes) if callable(value_ok) else value_ok
+        if vok is not None:
+            taken.set_value_ok(vok)
+        return taken, self.log.insert_device(taken.batch, taken.d_bitmap, taken.d_value_ok,
+                                             catch=catch, evidence=evidence)
 
     def advance_height(self, height: int) -> None:
         """The Process's own height change after a commit (process.go:710-725:

@@ -5,6 +5,7 @@
     q.insert_verified_device(dbatch, verdict, h)       # Replica.Run ingress: authenticated, filterHeight
     msgs, senders = q.consume(height, allowed)         # Consume(h, ..., procsAllowed)
     q.drop_below(height)                               # DropMessagesBelowHeight
+    taken = q.consume_device(height, allowed)          # Consume with the delivery left on the device (Taken)
 
 Queues are keyed by the message's From (mq.go:107-113); ``allowed`` is
 procsAllowed, applied at consume time (mq.go:49-51): a list / array of
@@ -20,7 +21,7 @@ import numpy as np
 from . import _lib
 from ._lib import HdBatchOut
 from .device import DeviceBatch, _torch, work_stream
-from .verify import Batch, Verifier
+from .verify import PROPOSE, Batch, Verifier
 
 
 def _sig_array(allowed) -> np.ndarray:
@@ -187,3 +188,114 @@ class MessageQueue:
 
     def drop_below(self, height: int) -> None:
         self._check(self._lib.hd_mq_drop_below(self._q, int(height)), "hd_mq_drop_below")
+
+    def consume_device(self, height: int, allowed=None) -> "Taken":
+        """consume() with the delivery left on the device (include/hd_mq.h
+        hd_mq_consume_device): the same removal, procsAllowed rule and order.
+        The returned :class:`Taken` is a view of memory the queue owns, shaped
+        as the inputs of every ``*_device`` call of the log, decide and tally
+        families; only the proposes come to the host.  It stays valid until
+        the next call on this queue other than the Taken's own methods,
+        ``len()`` and ``senders``.  ``last_removed`` is set as consume sets it."""
+        p = lambda x: x.ctypes.data
+        if allowed is None:
+            al, na = None, 0
+        else:
+            arr = _sig_array(allowed)
+            al, na = (p(arr) if len(arr) else p(np.zeros((1, 32), np.uint8))), len(arr)
+        t = _lib.HdMqTaken()
+        self._check(self._lib.hd_mq_consume_device(self._q, int(height), al, na, ctypes.byref(t)),
+                    "hd_mq_consume_device")
+        self.last_removed = int(t.removed)
+        return Taken(self, t)
+
+
+_PROPOSE_ROW = np.dtype([("index", "<u4"), ("sender", "<i4"), ("height", "<i8"), ("round", "<i8"),
+                         ("valid_round", "<i8"), ("value", "u1", (32,)), ("frm", "u1", (32,))])
+
+
+class Proposes(Batch):
+    """The delivered proposes of a :class:`Taken` on the host, in delivery
+    order: a Batch (the signatures, which validator.Valid does not read, are
+    zeros; :meth:`Taken.read` at ``index`` has them) with ``index``, each
+    row's position in the delivery, and ``sender``, its sender-queue id."""
+    index: np.ndarray
+    sender: np.ndarray
+
+
+class _DeviceView:
+    """n items at a device address, for torch.as_tensor."""
+
+    def __init__(self, ptr: int, n: int, typestr: str):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (int(ptr), False), "version": 2}
+
+
+class Taken:
+    """One consume_device: n delivered messages in device memory the queue owns.
+
+    n, removed: delivered; removed, delivered or not (Consume's n).
+    batch: an HdBatch of device pointers (n rows, delivery order).
+    d_bitmap, d_value_ok, d_sender: device addresses of the valid bitmap
+    (ceil(n/32) words, every message's bit set), the value_ok bytes (all 1
+    until set_value_ok) and the int32 sender-queue ids.
+    proposes: the delivered proposes on the host (:class:`Proposes`)."""
+    __slots__ = ("_mq", "n", "removed", "batch", "d_bitmap", "d_value_ok", "d_sender", "proposes")
+
+    def __init__(self, mq: MessageQueue, t: "_lib.HdMqTaken"):
+        self._mq = mq
+        self.n, self.removed = int(t.n), int(t.removed)
+        self.batch = _lib.HdBatch(t.batch.n, t.batch.type, t.batch.height, t.batch.round, t.batch.valid_round,
+                                  t.batch.value32, t.batch.from32, t.batch.sig65)
+        self.d_bitmap, self.d_value_ok, self.d_sender = t.d_valid_bitmap, t.d_value_ok, t.d_sender
+        k = int(t.n_proposes)
+        rows = (np.frombuffer(ctypes.string_at(t.proposes, _PROPOSE_ROW.itemsize * k), dtype=_PROPOSE_ROW)
+                if k else np.zeros(0, _PROPOSE_ROW))
+        pr = Proposes._wrap(np.full(k, PROPOSE, np.uint8), rows["height"].copy(), rows["round"].copy(),
+                            rows["valid_round"].copy(), rows["value"].copy(), rows["frm"].copy(),
+                            np.zeros((k, 65), np.uint8))
+        pr.index, pr.sender = rows["index"].copy(), rows["sender"].copy()
+        self.proposes = pr
+
+    def __len__(self) -> int:
+        return self.n
+
+    def set_value_ok(self, propose_ok) -> None:
+        """validator.Valid's answer per delivered propose (hd_mq_taken_value_ok):
+        d_value_ok[proposes.index[k]] = propose_ok[k], in stream order on the
+        verifier's stream, where an insert_device with stream None reads it."""
+        ok = np.ascontiguousarray(propose_ok, dtype=np.uint8).reshape(-1)
+        self._mq._check(self._mq._lib.hd_mq_taken_value_ok(self._mq._q, ok.ctypes.data if len(ok) else None, len(ok)),
+                        "hd_mq_taken_value_ok")
+
+    def read(self, idx=None, first: int = 0, n: Optional[int] = None) -> Tuple[Batch, np.ndarray]:
+        """hd_mq_taken_read: rows ``idx`` of the delivery (any order, repeats
+        allowed), or rows first .. first + n - 1 (n None: to the end), as host
+        (Batch, senders)."""
+        pos = None
+        if idx is not None:
+            pos = np.ascontiguousarray(idx, dtype=np.uint32)
+            n = len(pos)
+        elif n is None:
+            n = max(self.n - first, 0)
+        m = max(n, 1)
+        a = (np.empty(m, np.uint8), np.empty(m, np.int64), np.empty(m, np.int64), np.empty(m, np.int64),
+             np.empty((m, 32), np.uint8), np.empty((m, 32), np.uint8), np.empty((m, 65), np.uint8))
+        snd = np.empty(m, np.int32)
+        out = HdBatchOut(*(x.ctypes.data for x in a), None)
+        self._mq._check(self._mq._lib.hd_mq_taken_read(self._mq._q, pos.ctypes.data if pos is not None else None,
+                                                       int(first), n, ctypes.byref(out), snd.ctypes.data),
+                        "hd_mq_taken_read")
+        return Batch._wrap(*(x[:n] for x in a)), snd[:n]
+
+    def tensors(self):
+        """torch views (no copy) of value_ok (uint8[n]), the bitmap
+        (int32[ceil(n/32)]) and the senders (int32[n]); as short-lived as the
+        Taken itself."""
+        torch = _torch()
+        dev = torch.device("cuda", self._mq._v.device)
+        if self.n == 0:
+            e = lambda dt: torch.empty(0, dtype=dt, device=dev)
+            return e(torch.uint8), e(torch.int32), e(torch.int32)
+        view = lambda ptr, n, ts: torch.as_tensor(_DeviceView(ptr, n, ts), device=dev)
+        return (view(self.d_value_ok, self.n, "|u1"), view(self.d_bitmap, (self.n + 31) // 32, "<i4"),
+                view(self.d_sender, self.n, "<i4"))

@@ -353,6 +353,20 @@ def _caught_fields(c, arrs) -> Dict[str, np.ndarray]:
     return {"caught_" + k: arrs[k][: c.n].copy() for k in ("index", "against", "kind")}
 
 
+class _DeviceBytes:
+    """n bytes at a device address, where insert_device takes a tensor."""
+    __slots__ = ("ptr", "n")
+
+    def __init__(self, ptr: int, n: int):
+        self.ptr, self.n = ptr, n
+
+    def data_ptr(self) -> int:
+        return self.ptr
+
+    def numel(self) -> int:
+        return self.n
+
+
 class DecideLog:
     """A height's vote and propose logs kept on the device across inserts
     (include/hd_log.h): every insert returns what decide_ordered would return
@@ -508,14 +522,17 @@ class DecideLog:
                       catch: bool = False, evidence: bool = False) -> LogInsertResult:
         """hd_log_insert_device_bitmap over a device batch and the valid bitmap
         of verify_batch_device (bit i is message i of `dbatch`).  value_ok: a
-        torch uint8 tensor on the device, or a host array, which is uploaded
-        first.  catch, evidence: as :meth:`insert`."""
+        torch uint8 tensor on the device, the device address of n bytes (an
+        int: mq.Taken.d_value_ok), or a host array, which is uploaded first.
+        catch, evidence: as :meth:`insert`."""
         import torch
         if evidence and not catch:
             raise ValueError("evidence=True needs catch=True")
         n = dbatch.n
         vok = value_ok
-        if vok is not None and not isinstance(vok, torch.Tensor):
+        if isinstance(vok, int):
+            vok = _DeviceBytes(vok, n)
+        if vok is not None and not isinstance(vok, (torch.Tensor, _DeviceBytes)):
             vok = torch.from_numpy(np.ascontiguousarray(vok, dtype=np.uint8)).cuda()
             torch.cuda.current_stream().synchronize()
         if vok is not None and vok.numel() != n:

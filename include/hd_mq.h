@@ -91,6 +91,62 @@ int hd_mq_consume_votes(hd_mq* q, struct hd_votes* v, int64_t h, const uint8_t* 
 /* DropMessagesBelowHeight (mq.go:70-83): remove every message with height < h */
 int hd_mq_drop_below(hd_mq* q, int64_t h);
 
+/* ---- Consume into device memory ------------------------------------------
+ * The flush without the host round trip of the batch: the delivered messages
+ * stay in a device region the queue owns, shaped as the inputs of every
+ * *_device_bitmap call (hd_log_insert_device_bitmap and its catch / evidence
+ * forms, hd_decide*_device_bitmap, hd_tally_device_bitmap): a device hd_batch,
+ * its valid bitmap (every consumed message was authenticated at ingress) and
+ * a value_ok byte per message.  Only the proposes come to the host, because
+ * validator.Valid is the caller's: it answers with hd_mq_taken_value_ok. */
+typedef struct {             /* 96 bytes, no padding */
+    uint32_t index;          /* position in the delivery */
+    int32_t  sender;         /* sender-queue id, as out_sender */
+    int64_t  height, round, valid_round;
+    uint8_t  value32[32], from32[32];
+} hd_mq_propose;
+
+typedef struct {
+    uint32_t n, removed;             /* delivered; removed, delivered or not (Consume's n) */
+    hd_batch batch;                  /* DEVICE columns of n rows, delivery order; valid_round and sig65 always present */
+    const int32_t*  d_sender;        /* device, n */
+    const uint32_t* d_valid_bitmap;  /* device, ceil(n/32) words, bit i set for every i < n */
+    uint8_t*        d_value_ok;      /* device, n bytes, all 1 after the consume */
+    uint32_t n_proposes;
+    const hd_mq_propose* proposes;   /* HOST (pinned, queue-owned): the delivered proposes in delivery order */
+} hd_mq_taken;
+
+/* hd_mq_consume with the delivery left on the device: the same removal, the
+ * same procsAllowed rule (allowed32 == NULL: the ctx's admitted set now) and
+ * the same delivery order.  The region is the queue's own and sized by it, so
+ * there is no HD_ECAP; an allocation that fails returns HD_ENOMEM with
+ * nothing removed.  Returns when all its work has completed on the ctx's
+ * stream.  With n == 0 the call is HD_OK with `removed` set, and the pointers
+ * may be NULL.  HD_EINVAL for NULL arguments or allowed32 == NULL with
+ * n_allowed != 0, before any device work; a failed queue refuses as in every
+ * other call.
+ *
+ * Lifetime: *out's device columns, the propose rows and d_value_ok stay valid
+ * until the next call on q other than hd_mq_taken_*, hd_mq_size and
+ * hd_mq_senders; that call ends the delivery. */
+int hd_mq_consume_device(hd_mq* q, int64_t h, const uint8_t* allowed32, uint32_t n_allowed, hd_mq_taken* out);
+
+/* validator.Valid's answers for the delivered proposes:
+ * d_value_ok[proposes[k].index] = propose_ok[k].  The host bytes are copied
+ * before the call returns; the scatter is queued on the ctx's stream and not
+ * waited for, so a *_device_bitmap call on that stream (stream NULL) reads
+ * the answers.  HD_EINVAL when n_proposes is not the current delivery's
+ * count, or when there is no delivery. */
+int hd_mq_taken_value_ok(hd_mq* q, const uint8_t* propose_ok, uint32_t n_proposes);
+
+/* The delivery's hd_log_read: rows first .. first + n - 1 (idx == NULL), or
+ * rows idx[0 .. n-1] (host; any order, repeats allowed), into the HOST arrays
+ * of *out (valid_round, sig65 and adv_class may be NULL) and out_sender (may
+ * be NULL): one gather, one download.  HD_EINVAL for a row >= the delivery's
+ * n or no delivery, before any device work. */
+int hd_mq_taken_read(hd_mq* q, const uint32_t* idx, uint32_t first, uint32_t n, const hd_batch_out* out,
+                     int32_t* out_sender);
+
 #ifdef __cplusplus
 }
 #endif
