@@ -141,6 +141,22 @@ class HdEvidenceOut(ctypes.Structure):
     _fields_ = [("offender", HdLogRows), ("against", HdLogRows)]
 
 
+HD_LOG_SEL_VALUE, HD_LOG_SEL_FROM = 1, 2
+
+
+class HdLogFilter(ctypes.Structure):
+    """include/hd_log.h hd_log_filter (hd_log_select*)."""
+    _fields_ = [("round_lo", ctypes.c_int64), ("round_hi", ctypes.c_int64), ("type_mask", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("pos_lo", ctypes.c_uint32), ("pos_hi", ctypes.c_uint32),
+                ("limit", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("value32", ctypes.c_uint8 * 32),
+                ("from32", ctypes.c_uint8 * 32)]
+
+
+class HdLogSelected(ctypes.Structure):
+    """include/hd_log.h hd_log_selected (hd_log_select*)."""
+    _fields_ = [("total", ctypes.c_uint32), ("n", ctypes.c_uint32)]
+
+
 class HdMqPropose(ctypes.Structure):
     """include/hd_mq.h hd_mq_propose: one delivered propose (96 bytes)."""
     _fields_ = [("index", ctypes.c_uint32), ("sender", ctypes.c_int32), ("height", ctypes.c_int64),
@@ -277,6 +293,11 @@ SIGNATURES = {
                                                             ctypes.POINTER(HdDecideOrder), ctypes.POINTER(HdLogInfo),
                                                             ctypes.POINTER(HdCatchOut),
                                                             ctypes.POINTER(HdEvidenceOut), ctypes.c_void_p]),
+    "hd_log_select": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdLogFilter), ctypes.c_void_p, ctypes.c_uint32,
+                                     ctypes.POINTER(HdLogRows), ctypes.POINTER(HdLogSelected)]),
+    "hd_log_select_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdLogFilter),
+                                            ctypes.POINTER(HdBatchOut), ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_uint32, ctypes.POINTER(HdLogSelected), ctypes.c_void_p]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

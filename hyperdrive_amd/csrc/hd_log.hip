@@ -51,6 +51,23 @@
 //                   count from the stage header); record k fills records 2k
 //                   and 2k + 1 of the evidence block, which follows the classes
 //                   in the stage and comes down with them
+//
+// hd_log_select reads the retained entries by key (type, round range, value,
+// From; hd_logselect.h holds the predicate and the rank arithmetic, which
+// tests/native/hd_logselect_check.cpp replays on the host).  One lane per
+// position of [pos_lo, min(pos_hi, L)), blocks of 256, two passes in the shape
+// of k_log_count / k_log_keep:
+//
+//   k_log_sel_count  each block's number of matching entries
+//   k_log_sel_emit   match number j, in ascending position, goes to slot j: a
+//                    block's offset is the sum of the preceding blocks' counts
+//                    (no ticket, no device-scope release), a lane's slot that
+//                    plus the wavefronts before it plus its ballot prefix.  A
+//                    lane stores only below min(limit or infinity, cap).  The
+//                    host form packs one record per slot (pack_row's layout,
+//                    the position in the record's last word); the device form
+//                    scatters the row into the caller's columns.  The last
+//                    block leaves [total, n] in the stage header.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -59,6 +76,7 @@
 
 #include "../../include/hd_log.h"
 #include "hd_internal.h"
+#include "hd_logselect.h"
 
 using namespace hd;
 
@@ -111,6 +129,9 @@ struct hd_log {
     uint32_t guess_ev = 256;      // records of evidence staged with the classes; more take a second copy
     DevBuf pos;                   // hd_log_read: the asked positions
     hipStream_t commit_stream = nullptr;   // the caller's stream the last k_log_commit went on, if it was one
+    DevBuf sel_blk;               // hd_log_select: one count per block of 256 looked-at positions
+    uint32_t guess_sel = 256;     // records of a selection staged with its header; more take a second copy
+    hipEvent_t sel_ev = nullptr;  // orders a selection on a caller's stream after the context's stream
 };
 
 __device__ __forceinline__ void copy_row(const LogCols& dst, size_t j, const uint8_t* type, const int64_t* height,
@@ -287,6 +308,91 @@ __global__ __launch_bounds__(256) void k_log_evidence(DecideRecs r, uint32_t roo
             uint2* z = reinterpret_cast<uint2*>(dst);
             for (uint32_t w = 0; w < row_bytes / 8; w++) z[w] = make_uint2(0u, 0u);
         }
+    }
+}
+
+// ---------------------------------------------------------------- hd_log_select
+// the device form's outputs: the caller's columns of cap rows (vround, sig, vok, pos: each may be NULL)
+struct SelCols {
+    uint8_t* type;
+    int64_t* height;
+    int64_t* round;
+    int64_t* vround;
+    uint8_t* value32;
+    uint8_t* from32;
+    uint8_t* sig;
+    uint8_t* vok;
+    uint32_t* pos;
+};
+
+// entry q against the filter; q < L, so the row is a retained entry's (16-byte aligned: row 32 q of a hipMalloc)
+__device__ __forceinline__ bool sel_match(const hd_log_filter& f, const LogCols& lg, uint32_t q) {
+    const uint8_t* v = static_cast<const uint8_t*>(__builtin_assume_aligned(lg.value32 + 32 * (size_t)q, 16));
+    const uint8_t* s = static_cast<const uint8_t*>(__builtin_assume_aligned(lg.from32 + 32 * (size_t)q, 16));
+    return log_match(f, lg.type[q], lg.round[q], v, s);
+}
+
+// one block per 256 positions of [lo, end), in both passes below; end <= L
+__global__ __launch_bounds__(256) void k_log_sel_count(hd_log_filter f, uint32_t lo, uint32_t end, LogCols lg,
+                                                       uint32_t* __restrict__ blk) {
+    __shared__ uint32_t wn[LOG_SEL_WAVES];
+    const uint32_t q = lo + blockIdx.x * LOG_SEL_BLOCK + threadIdx.x;
+    const bool m = q < end && sel_match(f, lg, q);
+    const unsigned long long bal = __ballot(m);
+    if ((threadIdx.x & 63) == 0) wn[threadIdx.x >> 6] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) blk[blockIdx.x] = wn[0] + wn[1] + wn[2] + wn[3];
+}
+
+// HOST: slot j is record j of recs (rec_bytes each: a packed row with the position in its last word, or, with
+// rows == false, the position alone).  Otherwise slot j is row j of the caller's columns.  room <= cap slots exist.
+template <bool HOST>
+__global__ __launch_bounds__(256) void k_log_sel_emit(hd_log_filter f, uint32_t lo, uint32_t end,
+                                                      const uint32_t* __restrict__ blk, LogCols lg, uint32_t room,
+                                                      uint8_t* __restrict__ recs, uint32_t rec_bytes, bool rows,
+                                                      bool sig, SelCols o, uint32_t* __restrict__ hdr) {
+    __shared__ uint32_t part[LOG_SEL_WAVES], wn[LOG_SEL_WAVES];
+    const uint32_t w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t sn = log_sel_partial(blk, blockIdx.x, threadIdx.x);
+    for (int d = 32; d > 0; d >>= 1) sn += (uint32_t)__shfl_xor((int)sn, d, 64);
+    const uint32_t q = lo + blockIdx.x * LOG_SEL_BLOCK + threadIdx.x;
+    const bool m = q < end && sel_match(f, lg, q);
+    const unsigned long long bal = __ballot(m);
+    if (lane == 0) {
+        part[w] = sn;
+        wn[w] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    const uint32_t off = part[0] + part[1] + part[2] + part[3];
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
+        const uint32_t total = off + wn[0] + wn[1] + wn[2] + wn[3];
+        hdr[0] = total;
+        hdr[1] = log_sel_n(total, f.limit);
+    }
+    if (!m) return;
+    const uint32_t j = log_sel_rank(off, wn, w, bal, lane);
+    if (j >= room) return;   // past the limit, or no slot: nothing is stored at or beyond cap
+    if (HOST) {
+        uint8_t* dst = recs + (size_t)rec_bytes * j;
+        if (rows) pack_row(dst, lg, q, sig);
+        *reinterpret_cast<uint32_t*>(dst + rec_bytes - 4) = q;
+    } else {
+        o.type[j] = lg.type[q];
+        o.height[j] = lg.height[q];
+        o.round[j] = lg.round[q];
+        if (o.vround) o.vround[j] = lg.vround[q];
+        const uint4* v = reinterpret_cast<const uint4*>(lg.value32 + 32 * (size_t)q);
+        const uint4* s = reinterpret_cast<const uint4*>(lg.from32 + 32 * (size_t)q);
+        uint4* dv = reinterpret_cast<uint4*>(o.value32 + 32 * (size_t)j);
+        uint4* ds = reinterpret_cast<uint4*>(o.from32 + 32 * (size_t)j);
+        const uint4 v0 = v[0], v1 = v[1], s0 = s[0], s1 = s[1];
+        dv[0] = v0;
+        dv[1] = v1;
+        ds[0] = s0;
+        ds[1] = s1;
+        if (o.sig) copy_sig(o.sig, j, lg.sig, q);
+        if (o.vok) o.vok[j] = lg.vok[q];
+        if (o.pos) o.pos[j] = q;
     }
 }
 
@@ -589,9 +695,10 @@ int hd_log_destroy(hd_log* lg) {
     (void)hipDeviceSynchronize();   // a commit's copies may still be queued on a caller's stream
     cols_free(lg->lg);
     cols_free(lg->tmp);
-    DevBuf* bufs[] = {&lg->vd, &lg->dup, &lg->pclass, &lg->blk, &lg->res, &lg->in_vok, &lg->pos};
+    DevBuf* bufs[] = {&lg->vd, &lg->dup, &lg->pclass, &lg->blk, &lg->res, &lg->in_vok, &lg->pos, &lg->sel_blk};
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
+    if (lg->sel_ev) (void)hipEventDestroy(lg->sel_ev);
     if (lg->d_sched) (void)hipFree(lg->d_sched);
     if (lg->host) (void)hipHostFree(lg->host);
     delete lg;
@@ -713,6 +820,127 @@ int hd_log_read(hd_log* lg, const uint32_t* pos, uint32_t first, uint32_t n, hd_
     for (uint32_t k = 0; k < n; k++) unpack_row(lg->host + (size_t)row * k, out, k);
     out->n = n;
     return HD_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------- hd_log_select
+// The selection's kernels go on s behind the last insert's commit.  That commit went on the context's stream
+// or on a caller's (commit_stream, with the event hd_ctx_note_stream recorded behind it, as hd_log_read waits
+// for it); a selection on a caller's stream is ordered after the context's stream by an event of the log's own.
+static int sel_order(hd_log* lg, hipStream_t s) {
+    hd_ctx* ctx = lg->ctx;
+    if (lg->commit_stream && lg->commit_stream != s) {
+        for (const auto& se : ctx->caller_ev)
+            if (se.first == lg->commit_stream) LCHK(hipStreamWaitEvent(s, se.second, 0), "log select wait");
+    }
+    if (s == ctx->stream) {
+        lg->commit_stream = nullptr;   // the context's stream is behind it from here on
+        return HD_OK;
+    }
+    if (!lg->sel_ev) LCHK(hipEventCreateWithFlags(&lg->sel_ev, hipEventDisableTiming), "log select event");
+    LCHK(hipEventRecord(lg->sel_ev, ctx->stream), "log select record");
+    LCHK(hipStreamWaitEvent(s, lg->sel_ev, 0), "log select wait");
+    return HD_OK;
+}
+
+// rows / pos_out (host) or dev (device columns); want: an output was asked for
+static int log_select(hd_log* lg, const hd_log_filter* flt, uint32_t* pos_out, hd_log_rows* rows, const SelCols* dev,
+                      bool want, uint32_t cap, hd_log_selected* sel, hipStream_t s) {
+    hd_ctx* ctx = lg->ctx;
+    const hd_log_filter f = *flt;
+    const uint32_t end = log_sel_end(f.pos_hi, lg->L), nb = log_sel_blocks(f.pos_lo, end);
+    if (nb == 0 || f.round_lo > f.round_hi) return HD_OK;   // nothing to look at
+    (void)hipSetDevice(ctx->device);
+    const uint32_t room = want ? log_sel_room(f.limit, cap) : 0u;
+    const bool sig = rows && rows->sig65;
+    const uint32_t rec = dev ? 0u : rows ? (sig ? ROW_BYTES_SIG : ROW_BYTES) : 4u;
+    const uint32_t staged = dev ? 0u : std::min(lg->guess_sel, room);
+    const size_t hdr_bytes = 64;
+    int rc = buf_grow(ctx, lg->sel_blk, 4 * (size_t)nb);
+    if (!rc) rc = buf_grow(ctx, lg->res, hdr_bytes + (size_t)rec * room);
+    if (!rc) rc = host_grow(lg, hdr_bytes + (size_t)rec * staged);
+    if (!rc) rc = sel_order(lg, s);
+    if (rc) return rc;
+    uint32_t* blk = (uint32_t*)lg->sel_blk.p;
+    char* res = (char*)lg->res.p;
+    k_log_sel_count<<<nb, 256, 0, s>>>(f, f.pos_lo, end, lg->lg, blk);
+    if (dev)
+        k_log_sel_emit<false><<<nb, 256, 0, s>>>(f, f.pos_lo, end, blk, lg->lg, room, nullptr, 0u, false, false, *dev,
+                                                (uint32_t*)res);
+    else
+        k_log_sel_emit<true><<<nb, 256, 0, s>>>(f, f.pos_lo, end, blk, lg->lg, room, (uint8_t*)(res + hdr_bytes), rec,
+                                               rows != nullptr, sig, SelCols{}, (uint32_t*)res);
+    LCHK(hipGetLastError(), "log select kernels");
+    (void)hd_ctx_note_stream(ctx, s);
+    LCHK(hipMemcpyAsync(lg->host, res, hdr_bytes + (size_t)rec * staged, hipMemcpyDeviceToHost, s),
+         "log select download");
+    LCHK(hipStreamSynchronize(s), "log select sync");
+    const uint32_t* hdr = reinterpret_cast<const uint32_t*>(lg->host);
+    const uint32_t n = hdr[1];
+    sel->total = hdr[0];
+    sel->n = n;
+    if (!want) return HD_OK;
+    if (!dev) lg->guess_sel = std::max<uint32_t>(256u, n + n / 4);   // also after HD_ECAP: the retry is staged
+    if (n > cap) return HD_ECAP;
+    if (dev) return HD_OK;
+    // n <= room: every returned match has its record on the device, the first `staged` of them here too
+    const auto spread = [&](const char* src, uint32_t k0, uint32_t cnt) {
+        for (uint32_t k = 0; k < cnt; k++) {
+            const char* r = src + (size_t)rec * k;
+            if (rows) unpack_row(r, rows, k0 + k);
+            if (pos_out) memcpy(pos_out + k0 + k, r + rec - 4, 4);
+        }
+    };
+    const uint32_t first = std::min(n, staged);
+    spread(lg->host + hdr_bytes, 0, first);
+    if (n > first) {   // past the staged records: a second copy, as the evidence block's overflow
+        const size_t more = (size_t)rec * (n - first);
+        rc = host_grow(lg, more);   // everything the stage held has been copied out by now
+        if (rc) return rc;
+        LCHK(hipMemcpyAsync(lg->host, res + hdr_bytes + (size_t)rec * first, more, hipMemcpyDeviceToHost, s),
+             "log select overflow");
+        LCHK(hipStreamSynchronize(s), "log select overflow sync");
+        spread(lg->host, first, n - first);
+    }
+    if (rows) rows->n = n;
+    return HD_OK;
+}
+
+extern "C" {
+
+int hd_log_select(hd_log* lg, const hd_log_filter* flt, uint32_t* pos_out, uint32_t cap, hd_log_rows* rows,
+                  hd_log_selected* sel) {
+    if (!lg || !lg->ctx || !flt || !sel || !log_filter_ok(*flt)) return HD_EINVAL;
+    if (rows && (!rows_ok(rows) || rows->cap < cap || (rows->sig65 && !lg->keep_sig))) return HD_EINVAL;
+    sel->total = sel->n = 0;
+    if (rows) rows->n = 0;
+    // rows of cap 0 hold nothing: with cap == 0 the call is the count-only form
+    const bool want = cap != 0 && (pos_out || rows);
+    return log_select(lg, flt, pos_out, cap ? rows : nullptr, nullptr, want, cap, sel, lg->ctx->stream);
+}
+
+int hd_log_select_device(hd_log* lg, const hd_log_filter* flt, const hd_batch_out* d_out, uint8_t* d_value_ok,
+                         uint32_t* d_pos, uint32_t cap, hd_log_selected* sel, void* stream) {
+    if (!lg || !lg->ctx || !flt || !sel || !log_filter_ok(*flt)) return HD_EINVAL;
+    SelCols o{};
+    if (d_out) {
+        if (d_out->sig65 && !lg->keep_sig) return HD_EINVAL;
+        if (cap && (!d_out->type || !d_out->height || !d_out->round || !d_out->value32 || !d_out->from32))
+            return HD_EINVAL;
+        if ((((uintptr_t)d_out->value32 | (uintptr_t)d_out->from32) & 15u) ||
+            (((uintptr_t)d_out->height | (uintptr_t)d_out->round | (uintptr_t)d_out->valid_round) & 7u) ||
+            ((uintptr_t)d_pos & 3u))
+            return HD_EINVAL;
+        o = SelCols{d_out->type,   d_out->height, d_out->round, d_out->valid_round, d_out->value32,
+                    d_out->from32, d_out->sig65,  d_value_ok,   d_pos};
+    } else if (cap) {
+        return HD_EINVAL;
+    }
+    sel->total = sel->n = 0;
+    const bool want = cap != 0;
+    return log_select(lg, flt, nullptr, nullptr, want ? &o : nullptr, want, cap, sel,
+                      stream ? (hipStream_t)stream : lg->ctx->stream);
 }
 
 }  // extern "C"

@@ -76,6 +76,31 @@ def decide(tally, height: int, round_: int, f: int, propose_value: Optional[byte
     return out
 
 
+def check_certificate(verifier, batch, height: int, round_: int, kind, value: bytes, f: int) -> bool:
+    """The receiving side of ``DecideLog.certificate``: are these messages
+    2f+1 signed votes of ``kind`` ("prevote" / "precommit", or the type) for
+    ``value`` at (height, round)?  The signatures are verified on the device
+    against ``verifier``'s signatory set (verify_batch); then, on the host:
+    every verdict is VALID, every message has the asked type, height, round
+    and value, the Froms are pairwise distinct, and there are at least 2f+1."""
+    mtype = {"prevote": PREVOTE, "precommit": PRECOMMIT}.get(kind, kind)
+    if mtype not in (PREVOTE, PRECOMMIT):
+        raise ValueError(f"{kind!r} is not a vote kind")
+    value = bytes(value)
+    n = len(batch)
+    if n < 2 * f + 1:
+        return False
+    verdict = verifier.verify_batch(batch, recovered=False).verdict
+    if any(int(v) != 0 for v in verdict):                              # VALID
+        return False
+    for i in range(n):
+        if (int(batch.type[i]), int(batch.height[i]), int(batch.round[i])) != (mtype, height, round_):
+            return False
+        if batch.value[i].tobytes() != value:
+            return False
+    return len({batch.frm[i].tobytes() for i in range(n)}) == n
+
+
 def decide_votes(votes, round_: int, f: int, propose_value: Optional[bytes] = None, propose_valid: bool = False,
                  propose_valid_round: int = INVALID_ROUND) -> Dict[str, bool]:
     """The same predicates as :func:`decide`, for the current height of an

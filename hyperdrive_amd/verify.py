@@ -385,6 +385,7 @@ class DecideLog:
         self.f = int(f)
         self._sched = None
         self._rows = 0                # rows of the last insert: the next has at most this many more than its batch
+        self._sel_cap = 256           # rows a select without a limit brings room for; HD_ECAP names the need
         self.keep_signatures = bool(keep_signatures)
         if keep_signatures:
             v._check(self._lib.hd_log_keep_signatures(h, 1), "hd_log_keep_signatures")
@@ -558,6 +559,178 @@ class DecideLog:
                                                              ctypes.byref(o), ctypes.byref(w), ctypes.byref(info),
                                                              stream), "hd_log_insert_device_bitmap")
         return self._result(n, o, a, when, until, logpos, info)
+
+    # ---- keyed reads (hd_log_select) ---------------------------------------
+    def _filter(self, types, round, value, sender, first, upto, limit):
+        from ._lib import HD_LOG_SEL_FROM, HD_LOG_SEL_VALUE, HdLogFilter
+        f = HdLogFilter()
+        f.type_mask = _type_mask(types)
+        if round is None:
+            f.round_lo, f.round_hi = -(1 << 63), (1 << 63) - 1
+        elif isinstance(round, (tuple, list)):
+            f.round_lo, f.round_hi = int(round[0]), int(round[1])
+        else:
+            f.round_lo = f.round_hi = int(round)
+        for name, flag, v in (("value32", HD_LOG_SEL_VALUE, value), ("from32", HD_LOG_SEL_FROM, sender)):
+            if v is not None:
+                raw = bytes(v) if not isinstance(v, np.ndarray) else v.tobytes()
+                if len(raw) != 32:
+                    raise ValueError(f"{name} needs 32 bytes")
+                f.flags |= flag
+                ctypes.memmove(getattr(f, name), raw, 32)
+        if first < 0 or limit < 0 or (upto is not None and upto < -1):
+            raise ValueError("first, upto and limit are log positions and a count")
+        f.pos_lo = int(first)
+        f.pos_hi = 0xFFFFFFFF if upto is None else min(int(upto) + 1, 0xFFFFFFFF)
+        f.limit = int(limit)
+        return f
+
+    def select(self, types, round=None, value=None, sender=None, first: int = 0, upto: Optional[int] = None,
+               limit: int = 0, rows: bool = True) -> "LogSelection":
+        """hd_log_select: the logged entries of ``types`` (PROPOSE / PREVOTE /
+        PRECOMMIT, their names, or several of them) in arrival order, narrowed
+        by ``round`` (r, or (lo, hi) inclusive), ``value`` and ``sender`` (32
+        bytes each) and to the log positions ``first`` .. ``upto``, both
+        inclusive (upto None: to the log's end).  ``limit`` = k returns the
+        first k matches; ``total`` counts them all either way.  rows=False
+        returns the positions alone."""
+        from ._lib import HD_ECAP, HdLogSelected
+        f = self._filter(types, round, value, sender, first, upto, limit)
+        sel = HdLogSelected()
+        cap = int(limit) if limit else self._sel_cap
+        while True:
+            pos = np.zeros(max(cap, 1), np.uint32)
+            r, a = _rows_struct(cap, self.keep_signatures) if rows else (None, None)
+            rc = self._lib.hd_log_select(self._log, ctypes.byref(f), _ptr(pos), cap,
+                                         ctypes.byref(r) if rows else None, ctypes.byref(sel))
+            if rc != HD_ECAP or sel.n <= cap:
+                break
+            cap = sel.n                                    # the need: the same call with room succeeds
+        self._v._check(rc, "hd_log_select")
+        if not limit:
+            self._sel_cap = max(256, sel.n + sel.n // 4)
+        batch, ok = _rows_batch(sel.n, a) if rows else (None, None)
+        return LogSelection(pos[: sel.n].copy(), int(sel.total), batch, ok)
+
+    def count(self, types, round=None, value=None, sender=None, first: int = 0, upto: Optional[int] = None) -> int:
+        """The count-only form of :meth:`select`: how many entries match.
+        Nothing but the counts comes down."""
+        from ._lib import HdLogSelected
+        f = self._filter(types, round, value, sender, first, upto, 0)
+        sel = HdLogSelected()
+        self._v._check(self._lib.hd_log_select(self._log, ctypes.byref(f), None, 0, None, ctypes.byref(sel)),
+                       "hd_log_select")
+        return int(sel.total)
+
+    def select_device(self, types, round=None, value=None, sender=None, first: int = 0, upto: Optional[int] = None,
+                      limit: int = 0, cap: Optional[int] = None, stream=None) -> "DeviceSelection":
+        """hd_log_select_device: the same selection left on the device as a
+        DeviceBatch (signatures on a log that keeps them, zero otherwise) with
+        its value_ok bytes and log positions, ready for codec.marshal_device,
+        verify_batch_device and the *_device calls.  ``cap``: rows to allocate
+        (default: ``limit``, or the count of a count-only call made first).
+        ``stream``: a torch stream (default: the work stream)."""
+        import torch
+        from ._lib import HdLogSelected
+        from .device import DeviceBatch, work_stream
+        f = self._filter(types, round, value, sender, first, upto, limit)
+        if cap is None:
+            cap = int(limit) if limit else self.count(types, round, value, sender, first, upto)
+        ws = stream or work_stream()
+        with torch.cuda.stream(ws):
+            db = DeviceBatch.empty(cap)
+            if not self.keep_signatures:
+                db.sig.zero_()
+            vok = torch.empty(cap, dtype=torch.uint8, device="cuda")
+            pos = torch.empty(cap, dtype=torch.int32, device="cuda")
+        co = db.c_out()
+        if not self.keep_signatures:
+            co.sig65 = None
+        co.adv_class = None
+        sel = HdLogSelected()
+        self._v._check(self._lib.hd_log_select_device(self._log, ctypes.byref(f), ctypes.byref(co), vok.data_ptr(),
+                                                      pos.data_ptr(), cap, ctypes.byref(sel), ws.cuda_stream),
+                       "hd_log_select_device")
+        n = sel.n
+        return DeviceSelection(db.rows(0, n), vok[:n], pos[:n], n, int(sel.total))
+
+    def proposal(self, round: int) -> Optional["LogSelection"]:
+        """``ProposeLogs[round]`` as a selection of one row, ``value_ok[0]``
+        being ``ProposeIsValid[round]``; None when the round has no logged
+        propose."""
+        s = self.select(PROPOSE, round, limit=1)
+        return s if len(s) else None
+
+    def votes(self, kind, round: int) -> "LogSelection":
+        """``PrevoteLogs[round]`` / ``PrecommitLogs[round]`` in arrival order."""
+        return self.select(_vote_kind(kind), round)
+
+    def vote_of(self, kind, round: int, sender) -> Optional["LogSelection"]:
+        """``PrevoteLogs[round][sender]`` / ``PrecommitLogs[round][sender]`` as
+        a selection of one row, or None."""
+        s = self.select(_vote_kind(kind), round, sender=sender, limit=1)
+        return s if len(s) else None
+
+    def certificate(self, kind, round: int, value, upto: Optional[int] = None) -> Optional["LogSelection"]:
+        """The first 2f+1 logged votes of ``kind`` for ``value`` in ``round``
+        at log positions <= ``upto`` (None: the whole log): the signed votes
+        behind a firing of commit or prevote_validround, for a peer to check
+        with quorum.check_certificate.  None when there are fewer.
+
+        ``upto`` is a log position.  A ``when`` of an insert's result that is
+        below that insert's ``base`` already is one; a ``when`` at or above
+        ``base`` is a batch index, and the message's position is
+        ``result.logpos[when - result.base]`` (the message at which a count
+        rule fires is a logged vote, so it has one)."""
+        q = 2 * self.f + 1
+        s = self.select(_vote_kind(kind), round, value=value, upto=upto, limit=q)
+        return s if len(s) == q else None
+
+
+@dataclass
+class LogSelection:
+    """What DecideLog.select returns: ``positions`` (uint32, ascending), the
+    rows as a Batch with their ``value_ok`` bytes (None with rows=False), and
+    ``total``, the matches there are whatever ``limit`` was."""
+    positions: np.ndarray
+    total: int
+    batch: Optional[Batch]
+    value_ok: Optional[np.ndarray]
+
+    def __len__(self) -> int:
+        return len(self.positions)
+
+
+@dataclass
+class DeviceSelection:
+    """What DecideLog.select_device returns: ``n`` rows on the device."""
+    batch: "object"          # device.DeviceBatch of n rows
+    value_ok: "object"       # torch uint8[n]
+    positions: "object"      # torch int32[n]
+    n: int
+    total: int
+
+
+_TYPE_NAMES = {"propose": PROPOSE, "prevote": PREVOTE, "precommit": PRECOMMIT}
+
+
+def _type_mask(types) -> int:
+    if isinstance(types, (int, np.integer, str)):
+        types = (types,)
+    mask = 0
+    for t in types:
+        t = _TYPE_NAMES.get(t) if isinstance(t, str) else int(t)
+        if t not in (PROPOSE, PREVOTE, PRECOMMIT):
+            raise ValueError(f"bad message type {t}")
+        mask |= 1 << t
+    return mask
+
+
+def _vote_kind(kind) -> int:
+    t = _TYPE_NAMES.get(kind, kind) if isinstance(kind, str) else int(kind)
+    if t not in (PREVOTE, PRECOMMIT):
+        raise ValueError(f"{kind!r} is not a vote kind")
+    return t
 
 
 class Verifier:

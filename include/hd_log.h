@@ -162,6 +162,63 @@ int hd_log_insert_evidence_device_bitmap(hd_log* log, const hd_batch* dbatch, co
                                          hd_log_info* info, hd_catch_out* caught, hd_evidence_out* evidence,
                                          void* stream);
 
+/* ---- keyed reads ------------------------------------------------------------
+ * The reference keeps its logs as maps and reads them by key: ProposeLogs[r],
+ * PrevoteLogs[r][from], every precommit of round r for value v
+ * (process/state.go:44-57).  hd_log_select is that read on the device: the
+ * entries of the asked types whose round lies in [round_lo, round_hi] and,
+ * when asked, whose value and From equal the filter's, in arrival order
+ * (ascending position).  With limit = k it returns the first k of them -- the
+ * 2f+1 votes behind a firing of commit are limit = 2f+1 over the positions up
+ * to the firing.  The log is unchanged. */
+#define HD_LOG_SEL_VALUE 1u
+#define HD_LOG_SEL_FROM 2u
+
+typedef struct {
+    int64_t  round_lo, round_hi;   /* inclusive; lo > hi selects nothing */
+    uint32_t type_mask;            /* bit t: entries of type t, t = 1 Propose, 2 Prevote, 3 Precommit */
+    uint32_t flags;                /* HD_LOG_SEL_VALUE: value32 must equal; HD_LOG_SEL_FROM: from32 must equal */
+    uint32_t pos_lo, pos_hi;       /* positions [pos_lo, pos_hi); pos_hi is clipped to the log's entries */
+    uint32_t limit;                /* 0: every match; k: the first k matches in arrival order */
+    uint32_t reserved;             /* 0 */
+    uint8_t  value32[32], from32[32];
+} hd_log_filter;
+
+typedef struct {
+    uint32_t total;   /* matches inside [pos_lo, pos_hi), whatever limit and cap are */
+    uint32_t n;       /* returned: min(total, limit or infinity) */
+} hd_log_selected;
+
+/* Host outputs.  pos_out: cap words or NULL; rows: NULL, or columns of
+ * rows->cap >= cap rows (sig65 only on a log that keeps signatures).  cap == 0
+ * with NULL outputs is the count-only form: nothing but the 8-byte header
+ * comes down.  One synchronisation of the context's stream while n stays
+ * within the staged guess (256 rows, or a quarter more than the last call
+ * returned; as the evidence block does it); a larger selection takes a second
+ * copy.
+ *
+ * HD_EINVAL before any device work for a NULL log, filter or sel, a type_mask
+ * of 0 or with bits outside 1..3, unknown flags, reserved != 0, rows without
+ * its arrays, rows->cap < cap, or sig65 on a log that keeps no signatures.
+ * HD_ECAP when n > cap and an output was asked for: sel holds the need,
+ * nothing was written, and the same call with enough room succeeds.  An empty
+ * log, an empty position range and round_lo > round_hi are HD_OK with zero
+ * matches. */
+int hd_log_select(hd_log* log, const hd_log_filter* flt, uint32_t* pos_out, uint32_t cap, hd_log_rows* rows,
+                  hd_log_selected* sel);
+
+/* Device outputs: d_out's columns (valid_round and sig65 may be NULL;
+ * adv_class is ignored), d_value_ok and d_pos (each may be NULL) hold cap
+ * rows; rows [0, sel->n) are written on `stream` (NULL: the context's), which
+ * is synchronised once to return the counts; no row at or beyond cap is ever
+ * written.  value32 and from32 must be 16-byte aligned and the int64 columns
+ * 8-byte aligned (HD_EINVAL otherwise; torch and hipMalloc buffers are).
+ * d_out may be NULL when cap == 0 (the count-only form).  The columns are
+ * inputs of hd_marshal_batch_device, hd_verify_batch_device and the
+ * *_device_bitmap calls as they stand.  Errors as hd_log_select. */
+int hd_log_select_device(hd_log* log, const hd_log_filter* flt, const hd_batch_out* d_out, uint8_t* d_value_ok,
+                         uint32_t* d_pos, uint32_t cap, hd_log_selected* sel, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
