@@ -157,6 +157,29 @@ class HdLogSelected(ctypes.Structure):
     _fields_ = [("total", ctypes.c_uint32), ("n", ctypes.c_uint32)]
 
 
+# include/hd_cert.h HD_CERT_*
+HD_CERT_OK, HD_CERT_SHORT, HD_CERT_BAD_SIGNATURE, HD_CERT_WRONG_FIELD, HD_CERT_REPEATED_SENDER = 0, 1, 2, 3, 4
+
+
+class HdCert(ctypes.Structure):
+    """include/hd_cert.h hd_cert: one certificate to check (64 bytes)."""
+    _fields_ = [("first", ctypes.c_uint32), ("count", ctypes.c_uint32), ("quorum", ctypes.c_uint32),
+                ("type", ctypes.c_uint8), ("reserved", ctypes.c_uint8 * 3), ("height", ctypes.c_int64),
+                ("round", ctypes.c_int64), ("value32", ctypes.c_uint8 * 32)]
+
+
+class HdCertResult(ctypes.Structure):
+    """include/hd_cert.h hd_cert_result (16 bytes)."""
+    _fields_ = [("status", ctypes.c_uint32), ("good", ctypes.c_uint32), ("first_bad", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class HdCertPlan(ctypes.Structure):
+    """include/hd_cert.h hd_cert_plan (hd_cert_plan_info)."""
+    _fields_ = [("in_lds", ctypes.c_uint32), ("blocks", ctypes.c_uint32), ("lds_bytes", ctypes.c_uint32),
+                ("lds_entries", ctypes.c_uint32), ("slice_bytes", ctypes.c_uint64), ("scratch_bytes", ctypes.c_uint64)]
+
+
 class HdMqPropose(ctypes.Structure):
     """include/hd_mq.h hd_mq_propose: one delivered propose (96 bytes)."""
     _fields_ = [("index", ctypes.c_uint32), ("sender", ctypes.c_int32), ("height", ctypes.c_int64),
@@ -298,6 +321,13 @@ SIGNATURES = {
     "hd_log_select_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdLogFilter),
                                             ctypes.POINTER(HdBatchOut), ctypes.c_void_p, ctypes.c_void_p,
                                             ctypes.c_uint32, ctypes.POINTER(HdLogSelected), ctypes.c_void_p]),
+    # include/hd_cert.h
+    "hd_check_certificates_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
+                                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "hd_check_certificates": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
+                                             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "hd_cert_plan_info": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HdCertPlan)]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

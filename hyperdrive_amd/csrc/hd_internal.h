@@ -35,6 +35,7 @@ struct DevBuf {
 struct TallyWork;  // hd_tally.hip
 struct HostPipe;   // hd_host.hip: hd_verify_submit pipelines
 struct FbWork;     // hd_fastverify.hip: known-key tables and fast-path scratch
+struct CertWork;   // hd_certcheck.hip: the certificate check's rows and table scratch
 
 struct hd_ctx {
     int device = 0;
@@ -62,6 +63,7 @@ struct hd_ctx {
     DevBuf bufs[BUF__COUNT];
     TallyWork* tally = nullptr;
     FbWork* fb = nullptr;
+    CertWork* cert = nullptr;
     bool fastpath = true;   // known-key fast path (HD_VERIFY_FASTPATH=0 disables)
     hipEvent_t ev_slow = nullptr;   // after the last full-recovery-only verify call (fast path off)
     HostPipe* host = nullptr;
@@ -98,6 +100,7 @@ void hd_tally_release(hd_ctx* ctx);
 int hd_tally_routed_dup_device(hd_ctx* ctx, const hd_batch* dbatch, const uint32_t* d_gidx, hd_tally_out* out,
                                uint8_t* dup_global, hipStream_t s);
 void hd_host_release(hd_ctx* ctx);
+void hd_cert_release(hd_ctx* ctx);
 
 // hd_decide's device form (hd_tally.hip), shared with the retained log (hd_log.hip)
 struct DecideIn {

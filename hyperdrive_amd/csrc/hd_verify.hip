@@ -301,6 +301,7 @@ int hd_ctx_destroy(hd_ctx* ctx) {
     hd_host_release(ctx);
     hd_tally_release(ctx);
     hd_fb_release(ctx);
+    hd_cert_release(ctx);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return HD_OK;

@@ -101,6 +101,53 @@ def check_certificate(verifier, batch, height: int, round_: int, kind, value: by
     return len({batch.frm[i].tobytes() for i in range(n)}) == n
 
 
+def check_certificates(verifier, batch, certs) -> list:
+    """Many certificates in one call (``Verifier.check_certificates``,
+    hd_check_certificates): ``certs`` are ``verify.CertSpec`` segments of
+    ``batch``.  One upload, one verification and one check launch for all of
+    them; entry k is True exactly when certificate k is at least ``quorum``
+    VALID votes of its kind for its value at its (height, round), from
+    pairwise distinct signatories, and nothing else -- what
+    :func:`check_certificate` answers for that segment alone."""
+    return verifier.check_certificates(batch, certs).ok
+
+
+def check_certificates_wire(verifier, kind, buf, certs):
+    """The same for certificates as they arrive: ``buf`` holds the records
+    ``codec.marshal_device(..., with_sig=True)`` (hd_marshal_batch_device)
+    produced for votes of one ``kind``, any number of certificates back to
+    back; ``certs`` name their segments by record index.  Upload ->
+    hd_unmarshal_batch_device -> hd_verify_batch_device ->
+    hd_check_certificates_device are queued on one stream, which is
+    synchronised once.  Returns the ``verify.CertCheck`` (``.ok`` is the list
+    of bool).  A record the buffer ends before decodes to zero bytes (unmarshal
+    status 1): its zero signature verifies as BAD_RS, so it is *not valid* to
+    the check."""
+    import numpy as np
+    import torch
+    from . import codec
+    from .device import DeviceBatch, work_stream
+    from .verify import _vote_kind
+    mtype = _vote_kind(kind)
+    raw = buf if isinstance(buf, torch.Tensor) else torch.from_numpy(np.frombuffer(bytes(buf), np.uint8).copy())
+    rec = codec.record_size(mtype, True)
+    n = (raw.numel() + rec - 1) // rec
+    ws = work_stream()
+    with torch.cuda.stream(ws):
+        d_buf = torch.zeros(max(raw.numel(), 16), dtype=torch.uint8, device="cuda")
+        d_buf[: raw.numel()].copy_(raw, non_blocking=True)
+        db = DeviceBatch.empty(n)
+        d_verdict = torch.empty(max(n, 1), dtype=torch.uint8, device="cuda")
+        d_signer = torch.empty(max(n, 1), dtype=torch.int32, device="cuda")
+        d_bitmap = torch.zeros((n + 31) // 32 + 1, dtype=torch.int32, device="cuda")
+    if n:
+        codec.unmarshal_device(verifier, mtype, d_buf[: raw.numel()], n, with_sig=True, stream=ws, sync=False, out=db)
+        verifier.verify_batch_device(db.c_struct(), d_verdict.data_ptr(), None, d_signer.data_ptr(),
+                                     d_bitmap.data_ptr(), ws.cuda_stream)
+    return verifier.check_certificates_device(db.c_struct(), d_bitmap.data_ptr(), d_signer.data_ptr(),
+                                              verifier.n_signatories, certs, ws.cuda_stream)
+
+
 def decide_votes(votes, round_: int, f: int, propose_value: Optional[bytes] = None, propose_valid: bool = False,
                  propose_valid_round: int = INVALID_ROUND) -> Dict[str, bool]:
     """The same predicates as :func:`decide`, for the current height of an

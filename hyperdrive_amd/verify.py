@@ -711,6 +711,68 @@ class DeviceSelection:
     total: int
 
 
+# statuses of check_certificates (include/hd_cert.h HD_CERT_*)
+CERT_OK, CERT_SHORT, CERT_BAD_SIGNATURE, CERT_WRONG_FIELD, CERT_REPEATED_SENDER = 0, 1, 2, 3, 4
+CERT_NAMES = ["OK", "SHORT", "BAD_SIGNATURE", "WRONG_FIELD", "REPEATED_SENDER"]
+
+
+@dataclass
+class CertSpec:
+    """One certificate to check (hd_cert): messages [first, first + count) of
+    a batch must be VALID votes of ``kind`` ("prevote" / "precommit", or the
+    type) for ``value`` at (height, round), from pairwise distinct
+    signatories, at least ``quorum`` (2f+1) of them."""
+    first: int
+    count: int
+    kind: object
+    height: int
+    round: int
+    value: bytes
+    quorum: int
+
+
+@dataclass
+class CertCheck:
+    """What check_certificates returns, one entry per certificate: ``status``
+    (CERT_*), ``good`` (distinct signatories among the clean messages) and
+    ``first_bad`` (batch index of the lowest offending message, 0xFFFFFFFF:
+    none), all uint32; ``verdict`` (uint8 per message of the batch) when
+    asked for."""
+    status: np.ndarray
+    good: np.ndarray
+    first_bad: np.ndarray
+    verdict: Optional[np.ndarray] = None
+
+    def __len__(self) -> int:
+        return len(self.status)
+
+    @property
+    def ok(self) -> List[bool]:
+        return [int(s) == CERT_OK for s in self.status]
+
+
+def cert_rows(certs):
+    """The hd_cert rows of a list of CertSpec, as a ctypes array.  Every call
+    that takes ``certs`` also takes such an array as it stands, so a caller
+    that checks the same segments again builds the rows once."""
+    if isinstance(certs, ctypes.Array):
+        return certs
+    rows = (_lib.HdCert * len(certs))()
+    for row, c in zip(rows, certs):
+        value = bytes(c.value)
+        if len(value) != 32:
+            raise ValueError("a certificate's value has 32 bytes")
+        row.first, row.count, row.quorum, row.type = int(c.first), int(c.count), int(c.quorum), _vote_kind(c.kind)
+        row.height, row.round = int(c.height), int(c.round)
+        ctypes.memmove(row.value32, value, 32)
+    return rows
+
+
+def _cert_check(res, k: int, verdict=None) -> CertCheck:
+    a = np.frombuffer(res, np.uint32).reshape(-1, 4)[:k]
+    return CertCheck(a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy(), verdict)
+
+
 _TYPE_NAMES = {"propose": PROPOSE, "prevote": PREVOTE, "precommit": PRECOMMIT}
 
 
@@ -972,6 +1034,48 @@ class Verifier:
         reference drops every unauthenticated message, process/process.go:95-98)."""
         self._check(self._lib.hd_authenticate_batch_device(self._ctx, ctypes.byref(dbatch), d_verdict, stream),
                     "hd_authenticate_batch_device")
+
+    # ---- certificates ---------------------------------------------------
+    def check_certificates(self, batch: Batch, certs, verdict: bool = False) -> CertCheck:
+        """hd_check_certificates: one upload of ``batch``, its verification
+        against this verifier's signatory set, and the check of every
+        certificate of ``certs`` (CertSpec segments of the batch, or their
+        cert_rows) in one launch behind
+        it; one synchronisation.  ``verdict=True`` also returns the
+        per-message verdicts, which say why a BAD_SIGNATURE message failed."""
+        rows = cert_rows(certs)
+        k = len(rows)
+        res = (_lib.HdCertResult * max(k, 1))()
+        vd = np.zeros(len(batch), np.uint8) if verdict else None
+        cb = batch.c_struct()
+        self._check(self._lib.hd_check_certificates(self._ctx, ctypes.byref(cb), rows, k, res, _ptr(vd)),
+                    "hd_check_certificates")
+        return _cert_check(res, k, vd)
+
+    def check_certificates_device(self, dbatch: HdBatch, d_bitmap: int, d_signer: int, n_signers: int,
+                                  certs, stream: Optional[int] = None) -> CertCheck:
+        """hd_check_certificates_device: the batch, the valid bitmap and the
+        signer indices are the device outputs of verify_batch_device;
+        ``n_signers`` is the size of the signatory set that verified them.
+        Queued on ``stream`` behind the verification, which is synchronised
+        once."""
+        rows = cert_rows(certs)
+        k = len(rows)
+        res = (_lib.HdCertResult * max(k, 1))()
+        self._check(self._lib.hd_check_certificates_device(self._ctx, ctypes.byref(dbatch), d_bitmap, d_signer,
+                                                           int(n_signers), rows, k, res, stream),
+                    "hd_check_certificates_device")
+        return _cert_check(res, k)
+
+    @staticmethod
+    def cert_plan(n_signers: int, k: int) -> dict:
+        """hd_cert_plan_info: where the check keeps its per-signer table and
+        the grid it launches (diagnostics)."""
+        p = _lib.HdCertPlan()
+        rc = _lib.load().hd_cert_plan_info(int(n_signers), int(k), ctypes.byref(p))
+        if rc != 0:
+            raise HDError(rc, "hd_cert_plan_info")
+        return {name: int(getattr(p, name)) for name, _ in p._fields_}
 
     # ---- tally -------------------------------------------------------
     @staticmethod
