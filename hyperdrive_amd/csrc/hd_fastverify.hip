@@ -38,6 +38,7 @@
 #include "hd_fixedbase.h"
 #include "hd_dedup.h"
 #include "hd_scmont.h"
+#include "hd_inv2.h"
 #include "hd_internal.h"
 #include "hd_keycarry.h"
 #include "hd_verify_msg.h"
@@ -71,6 +72,11 @@ struct FbWork {
     struct Scratch {
         uint32_t* rows = nullptr;     // the split check's per-message rows (SplitRows, 63 words per message)
         size_t cap_rows = 0;
+        // the two-level lean inversions' roots and roots-prefix rows (RootRows),
+        // 9 words x split_lanes<8>(n) each; the s pass and the Z pass of a call
+        // use them one after the other
+        uint32_t* roots = nullptr;
+        size_t cap_roots = 0;
         // the repeat table (hd_dedup.h): dd_table_words(n) message indices,
         // then the preimage table, as many: one allocation, cleared by one
         // memset over the tables the call uses
@@ -164,6 +170,11 @@ struct FbWork {
         }
     } sums;
     uint32_t n_capped = 0, n_lean = 0, n_chained = 0;   // hd_ctx_overlap_stats
+    // hd_ctx_inv_levels: the lean inversions in two levels (2) or as the one
+    // kernel each (1); inv_k2: roots per inverting lane (HD_INV_K2: 8 or 16).
+    // n_inv: lean calls that launched the two-level form, the one-level form.
+    int inv_levels = 2, inv_k2 = 16;
+    uint64_t n_inv[2] = {0, 0};
     // hd_ctx_profile: event pairs around whole calls and around k_fast_sums
     bool prof = false;
     std::vector<hipEvent_t> ev_call, ev_sums;
@@ -250,16 +261,8 @@ struct FastSrc {
 // T = ceil(n / K)), so every step j of a wave touches consecutive messages.
 // The verdicts are the ones verify_fast2 (hd_fixedbase.h, host-tested) gives:
 // same early checks, same sums, same comparison.
-#define HD_FAST_LIVE 0xFDu   // aux code: keep going (the rest are final verdicts or HD_NEEDS_SLOW)
-
-template <int NW>
-HD void soa_load(uint32_t (&w)[NW], const uint32_t* __restrict__ p, uint32_t n, uint32_t i) {
-    HD_UNROLL for (int k = 0; k < NW; k++) w[k] = p[(size_t)k * n + i];
-}
-template <int NW>
-HD void soa_store(uint32_t* __restrict__ p, uint32_t n, uint32_t i, const uint32_t (&w)[NW]) {
-    HD_UNROLL for (int k = 0; k < NW; k++) p[(size_t)k * n + i] = w[k];
-}
+// (HD_FAST_LIVE, the aux code "keep going", and soa_load / soa_store, a word-major
+// row's entry: hd_inv2.h)
 
 //
 // Repeats and compaction (hd_dedup.h).  k_fast_prep gives every
@@ -611,10 +614,7 @@ __global__ __launch_bounds__(256) void k_fast_prep(DevBatch b, const uint8_t* __
 // The slots in use come from k_fast_prep's counter; T, the lanes of the
 // K-per-lane kernels (a multiple of 64), follows from it in the kernel, so a
 // batch of repeats does not spread its few slots over lanes sized for n.
-template <int K>
-HD uint32_t split_lanes(uint32_t nc) {
-    return ((nc + (uint32_t)K - 1) / (uint32_t)K + 63u) & ~63u;
-}
+// (split_lanes<K>: hd_inv2.h)
 
 // (est / stats: the first lane stores the call's slot count for the host's
 // next launches and adds the call to the context's cumulative counters)
@@ -1002,6 +1002,86 @@ __global__ __launch_bounds__(256, 3) void k_fast_zinv_lean(uint32_t n, SplitRows
             soa_store(rows.pre, n, i, inv.n);
         }
     }
+}
+
+// The lean inversions in two levels (hd_ctx_inv_levels 2; hd_inv2.h): each
+// lean kernel as three kernels on the call's stream.  up is the lean walk's
+// first loop and leaves each lane's product in the roots row, mid runs the
+// lean walk over those T roots (K2 per lane, split_lanes<K2>(T) lanes: the
+// only lanes that invert), down is the walk's second loop from the root's
+// inverse.  A wave's divstep inversion costs the same whether 64 lanes need
+// it or one, so a call pays for 1 / K2 of the lean forms' inversions and for
+// about three more products per lane.  T and T2 follow from the slot counter
+// as T does above; the mid grids are sized from n like the others.  The same
+// slots come out of the same rows as in the lean forms.
+struct RootRows {
+    uint32_t* roots;   // 9 T: the lanes' products, then their inverses
+    uint32_t* rpre;    // 9 T: prefix products of the roots
+};
+
+template <int K>
+__global__ __launch_bounds__(256, 3) void k_fast_sinv_up(uint32_t n, SplitRows rows, RootRows rr,
+                                                         uint32_t* __restrict__ est,
+                                                         unsigned long long* __restrict__ stats) {
+    wave_prio(rows.prio);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
+    if (t == 0) {   // as k_fast_sinv
+        const uint32_t reps = rows.cnt[3];
+        if (est) {
+            est[1] = n;
+            est[0] = nc;
+        }
+        if (nc + reps) atomicAdd(&stats[0], (unsigned long long)nc + reps);
+        if (reps) atomicAdd(&stats[1], (unsigned long long)reps);
+    }
+    if (t >= T) return;
+    inv2_up<sm, K>(t, T, nc, n, rows.aux, rows.s, rows.pre, rr.roots);
+}
+
+template <int K2, int K>
+__global__ __launch_bounds__(256, 3) void k_fast_sinv_mid(SplitRows rows, RootRows rr) {
+    wave_prio(rows.prio);
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t T = split_lanes<K>(rows.cnt[2]), T2 = split_lanes<K2>(T);
+    if (u >= T2) return;
+    inv2_mid<sm, K2>(u, T2, T, rr.roots, rr.rpre);
+}
+
+template <int K>
+__global__ __launch_bounds__(256, 3) void k_fast_sinv_down(uint32_t n, SplitRows rows, RootRows rr) {
+    wave_prio(rows.prio);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
+    if (t >= T) return;
+    inv2_down<sm, K>(t, T, nc, n, rows.aux, rows.s, rows.pre, rr.roots);
+}
+
+template <int K>
+__global__ __launch_bounds__(256, 3) void k_fast_zinv_up(uint32_t n, SplitRows rows, RootRows rr) {
+    wave_prio(rows.prio);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
+    if (t >= T) return;
+    inv2_up<fe, K>(t, T, nc, n, rows.aux, rows.xyz + 18 * (size_t)n, rows.pre, rr.roots);
+}
+
+template <int K2, int K>
+__global__ __launch_bounds__(256, 3) void k_fast_zinv_mid(SplitRows rows, RootRows rr) {
+    wave_prio(rows.prio);
+    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t T = split_lanes<K>(rows.cnt[2]), T2 = split_lanes<K2>(T);
+    if (u >= T2) return;
+    inv2_mid<fe, K2>(u, T2, T, rr.roots, rr.rpre);
+}
+
+template <int K>
+__global__ __launch_bounds__(256, 3) void k_fast_zinv_down(uint32_t n, SplitRows rows, RootRows rr) {
+    wave_prio(rows.prio);
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t nc = rows.cnt[2], T = split_lanes<K>(nc);
+    if (t >= T) return;
+    inv2_down<fe, K>(t, T, nc, n, rows.aux, rows.xyz + 18 * (size_t)n, rows.pre, rr.roots);
 }
 
 // x = r (+ n when v & 2) as a field element: the x coordinate of R (the range
@@ -1645,6 +1725,8 @@ int hd_fb_init(hd_ctx* ctx) {
     // that owns its GPU may still set it.
     f->budget = 64.0 * (1ull << 30);
     if (const char* m = getenv("HD_FB_MAX_BYTES")) f->budget = atof(m);
+    if (const char* l = getenv("HD_INV_LEVELS")) f->inv_levels = atoi(l) == 1 ? 1 : 2;
+    if (const char* k2 = getenv("HD_INV_K2")) f->inv_k2 = atoi(k2) == 8 ? 8 : 16;
     f->max_slots = (uint32_t)std::max(1.0, std::min(1e6, f->budget / fb_slot_bytes(f->wp)));
     FBCHK(hipMalloc(&f->counts, 8), "fb counts");
     FBCHK(hipMalloc(&f->zr, fb_run_scratch_bytes(ctx)), "fb builder scratch");
@@ -1678,7 +1760,7 @@ void hd_fb_release(hd_ctx* ctx) {
     for (hipEvent_t e : f->ev_sums) (void)hipEventDestroy(e);
     for (auto& sc : f->sc) {
         if (sc.done) (void)hipEventDestroy(sc.done);
-        void* sp[] = {sc.rows, sc.slow, sc.count, sc.slow2, sc.dtab, sc.pre};
+        void* sp[] = {sc.rows, sc.slow, sc.count, sc.slow2, sc.dtab, sc.pre, sc.roots};
         for (void* p : sp)
             if (p) (void)hipFree(p);
     }
@@ -2080,7 +2162,18 @@ static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest
     // HD_VAR_LEAN_INV: the inversion kernels that fit beside a capped sums;
     // a call that takes the 4-wave sums (a small batch) keeps the register
     // forms and stays out of the chain below
-    if (p.lean) k_fast_sinv_lean<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
+    // hd_ctx_inv_levels 2: each lean kernel as up, mid, down (hd_inv2.h)
+    const bool two = p.lean && f->inv_levels == 2;
+    const uint32_t rt = split_lanes<8>(n);   // what the root rows hold; T <= split_lanes<K>(n) <= rt
+    const RootRows rr{sc.roots, two ? sc.roots + 9 * (size_t)rt : nullptr};
+    const bool k2w = f->inv_k2 == 8;
+    const uint32_t mb = ((k2w ? split_lanes<8>(split_lanes<K>(n)) : split_lanes<16>(split_lanes<K>(n))) + 255) / 256;
+    if (two) {
+        k_fast_sinv_up<K><<<tb, 256, 0, s>>>(n, rows, rr, f->est_dev + 2, f->dstats);
+        if (k2w) k_fast_sinv_mid<8, K><<<mb, 256, 0, s>>>(rows, rr);
+        else k_fast_sinv_mid<16, K><<<mb, 256, 0, s>>>(rows, rr);
+        k_fast_sinv_down<K><<<tb, 256, 0, s>>>(n, rows, rr);
+    } else if (p.lean) k_fast_sinv_lean<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
     else k_fast_sinv<K><<<tb, 256, 0, s>>>(n, rows, f->est_dev + 2, f->dstats);
     // HD_VAR_SUM_CHAIN (see FbWork): behind the previous call's sums when it
     // ran on another stream; before the profile pair, so the pair times the
@@ -2091,8 +2184,14 @@ static void launch_split(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_digest
     launch_sums<WP>(p, nb, s, n, f->gtab, f->tabs, rows);
     if (pe) (void)hipEventRecord(pe[1], s);
     if (p.chain) f->sums.record(s);
-    if (p.lean) k_fast_zinv_lean<K><<<tb, 256, 0, s>>>(n, rows);
+    if (two) {
+        k_fast_zinv_up<K><<<tb, 256, 0, s>>>(n, rows, rr);
+        if (k2w) k_fast_zinv_mid<8, K><<<mb, 256, 0, s>>>(rows, rr);
+        else k_fast_zinv_mid<16, K><<<mb, 256, 0, s>>>(rows, rr);
+        k_fast_zinv_down<K><<<tb, 256, 0, s>>>(n, rows, rr);
+    } else if (p.lean) k_fast_zinv_lean<K><<<tb, 256, 0, s>>>(n, rows);
     else k_fast_zinv<K><<<tb, 256, 0, s>>>(n, rows);
+    if (p.lean) f->n_inv[two ? 0 : 1]++;
     // whole blocks of 256: every wavefront's 64 messages are one bitmap word pair
     k_fast_cmp<<<nb, 256, 0, s>>>(b, rows, ctx->d_adm_perm, d_verdict, d_rec32, d_signer, sc.slow, sc.count,
                                   d_bitmap, auth);
@@ -2182,6 +2281,10 @@ static int fb_verify_impl(hd_ctx* ctx, const DevBatch& b, const uint8_t* d_diges
         }
         if (p.share) {
             rc = hd_dev_grow(ctx, (void**)&sc.pre, &sc.cap_pre, 40 * (size_t)n);
+            if (rc) return rc;
+        }
+        if (p.lean && f->inv_levels == 2) {   // RootRows: two rows of 9 words per level-1 lane
+            rc = hd_dev_grow(ctx, (void**)&sc.roots, &sc.cap_roots, 4 * 18 * (size_t)split_lanes<8>(n));
             if (rc) return rc;
         }
         SplitRows rows;
@@ -2372,6 +2475,20 @@ int hd_ctx_preimage_stats(hd_ctx* ctx, uint64_t* typed, uint64_t* distinct) {
     FBCHK(hipMemcpy(st, ctx->fb->pstats, 16, hipMemcpyDeviceToHost), "preimage counters read");
     if (typed) *typed = st[0];
     if (distinct) *distinct = st[1];
+    return HD_OK;
+}
+
+int hd_ctx_inv_levels(hd_ctx* ctx, int set) {
+    if (!ctx || !ctx->fb || (set != -1 && set != 1 && set != 2)) return HD_EINVAL;
+    if (set != -1) ctx->fb->inv_levels = set;
+    return ctx->fb->inv_levels;
+}
+
+int hd_ctx_inv_stats(hd_ctx* ctx, uint64_t out[2]) {
+    if (!ctx || !out) return HD_EINVAL;
+    const FbWork* f = ctx->fb;
+    out[0] = f ? f->n_inv[0] : 0;
+    out[1] = f ? f->n_inv[1] : 0;
     return HD_OK;
 }
 

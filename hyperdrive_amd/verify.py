@@ -972,6 +972,22 @@ class Verifier:
                     "hd_ctx_overlap_stats")
         return int(c.value), int(l.value), int(w.value)
 
+    def inv_levels(self, set: int = -1) -> int:
+        """Levels of the lean inversions (1 or 2); `set` 1 or 2 changes it for
+        the calls that follow (include/hd_verify.h hd_ctx_inv_levels)."""
+        got = self._lib.hd_ctx_inv_levels(self._ctx, set)
+        if got not in (1, 2):
+            self._check(got if got < 0 else -1, "hd_ctx_inv_levels")
+        return got
+
+    def inv_stats(self) -> Tuple[int, int]:
+        """(lean calls that launched the two-level inversions, lean calls that
+        launched the one-level kernels), cumulative
+        (include/hd_verify.h hd_ctx_inv_stats)."""
+        out = (ctypes.c_uint64 * 2)()
+        self._check(self._lib.hd_ctx_inv_stats(self._ctx, out), "hd_ctx_inv_stats")
+        return int(out[0]), int(out[1])
+
     def fastpath_geometry(self) -> Tuple[int, int, int]:
         """(G table windows, per-key table windows, messages sharing one
         inversion) of the known-key check as this context runs it."""

@@ -236,6 +236,24 @@ int hd_ctx_preimage_stats(hd_ctx* ctx, uint64_t* typed, uint64_t* distinct);
  * kernels, chained = calls whose k_fast_sums was made to wait for the
  * previous call's.  Any pointer may be NULL; host-only. */
 int hd_ctx_overlap_stats(hd_ctx* ctx, uint32_t* capped, uint32_t* lean, uint32_t* chained);
+/* Levels of the lean inversions (the calls hd_ctx_overlap_stats counts as
+ * lean).  2, the default: each of the two inversions runs as three kernels
+ * (up, mid, down), and one divstep inversion serves 8 or 16 lanes' products
+ * (16 unless the environment variable HD_INV_K2 is 8 at context creation)
+ * as well as each lane's 8 or 16 slots.  1: the one lean kernel per inversion,
+ * one divstep inversion per lane.  The outputs of a call are the same either
+ * way.  set = 1 or 2 sets the value for the calls submitted from then on,
+ * set = -1 only reads it; returns the value in force, or HD_EINVAL for a NULL
+ * context or any other set.  Taken at context creation from the environment
+ * variable HD_INV_LEVELS (1 or 2).  Not a variant key: the call plan and the
+ * variant table do not know it.  Host-only. */
+int hd_ctx_inv_levels(hd_ctx* ctx, int set);
+/* Lean calls by the form of their inversions, cumulative since context
+ * creation, counted on the host when the call is submitted: out[0] = calls
+ * that launched the two-level form, out[1] = calls that launched the
+ * one-level lean kernels (their sum is hd_ctx_overlap_stats' lean).
+ * HD_EINVAL for a NULL argument; host-only. */
+int hd_ctx_inv_stats(hd_ctx* ctx, uint64_t out[2]);
 /* Shape of the known-key check as the context runs it now (for cost models):
  * g_windows / key_windows: fixed-base windows of the G table and of the
  * per-key tables (one table point each; the first is loaded, the rest are
