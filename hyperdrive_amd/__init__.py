@@ -7,10 +7,10 @@ The compute lives in ``_lib/libhdverify.so`` (HIP, gfx950) behind the C ABI of
 from .verify import (BAD_RECID, BAD_RS, BAD_TYPE, CATCH_NAMES, INFINITY, NO_POINT, NOT_ADMITTED, NOT_AUTHENTIC,
                      SIGNATORY_MISMATCH, VALID, WHEN_NEVER, Batch, CertCheck, CertSpec, CaughtDecideResult, CaughtLogInsertResult,
                      CaughtOrderedDecideResult, DecideLog, DecideResult, EvidenceLogInsertResult, LogInsertResult,
-                     OrderedDecideResult,
+                     OrderedDecideResult, SignatorySets,
                      TallyResult, Verifier, VerifyResult, probe_valu)
 
 __all__ = ["Batch", "Verifier", "VerifyResult", "TallyResult", "DecideResult", "OrderedDecideResult", "DecideLog",
            "LogInsertResult", "CaughtDecideResult", "CaughtOrderedDecideResult", "CaughtLogInsertResult",
-           "EvidenceLogInsertResult", "CertSpec", "CertCheck", "CATCH_NAMES", "WHEN_NEVER", "probe_valu", "VALID", "BAD_RECID", "BAD_RS",
+           "EvidenceLogInsertResult", "CertSpec", "CertCheck", "SignatorySets", "CATCH_NAMES", "WHEN_NEVER", "probe_valu", "VALID", "BAD_RECID", "BAD_RS",
            "NO_POINT", "INFINITY", "SIGNATORY_MISMATCH", "NOT_ADMITTED", "BAD_TYPE", "NOT_AUTHENTIC"]

@@ -159,6 +159,7 @@ class HdLogSelected(ctypes.Structure):
 
 # include/hd_cert.h HD_CERT_*
 HD_CERT_OK, HD_CERT_SHORT, HD_CERT_BAD_SIGNATURE, HD_CERT_WRONG_FIELD, HD_CERT_REPEATED_SENDER = 0, 1, 2, 3, 4
+HD_CERT_NOT_MEMBER = 5   # hd_check_certificates_sets only
 
 
 class HdCert(ctypes.Structure):
@@ -330,6 +331,20 @@ SIGNATURES = {
     "hd_check_certificates": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(HdBatch), ctypes.c_void_p,
                                              ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
     "hd_cert_plan_info": (ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(HdCertPlan)]),
+    "hd_check_certificates_sets_device": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HdBatch),
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]),
+    "hd_check_certificates_sets": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(HdBatch),
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p,
+                                                  ctypes.c_void_p]),
+    # include/hd_sigsets.h
+    "hd_sigsets_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
+    "hd_sigsets_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "hd_sigsets_add": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+                                      ctypes.POINTER(ctypes.c_uint32)]),
+    "hd_sigsets_clear": (ctypes.c_int, [ctypes.c_void_p]),
+    "hd_sigsets_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                       ctypes.POINTER(ctypes.c_uint32)]),
     "hd_multi_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
     "hd_multi_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "hd_multi_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),

@@ -112,7 +112,19 @@ def check_certificates(verifier, batch, certs) -> list:
     return verifier.check_certificates(batch, certs).ok
 
 
-def check_certificates_wire(verifier, kind, buf, certs):
+def check_certificates_sets(verifier, batch, certs, sets, set_of=None) -> list:
+    """The same under several signatory sets
+    (``Verifier.check_certificates_sets``, hd_check_certificates_sets):
+    certificate k is decided under set ``set_of[k]`` of ``sets`` (a
+    ``verify.SignatorySets``; ``set_of=None`` reads each CertSpec's ``set``),
+    not under the verifier's own set, which stays as it is.  Entry k is True
+    exactly when certificate k is at least ``quorum`` authentic votes of its
+    kind for its value at its (height, round), from pairwise distinct members
+    of its set, and nothing else."""
+    return verifier.check_certificates_sets(batch, certs, sets, set_of).ok
+
+
+def check_certificates_wire(verifier, kind, buf, certs, sets=None, set_of=None):
     """The same for certificates as they arrive: ``buf`` holds the records
     ``codec.marshal_device(..., with_sig=True)`` (hd_marshal_batch_device)
     produced for votes of one ``kind``, any number of certificates back to
@@ -122,7 +134,13 @@ def check_certificates_wire(verifier, kind, buf, certs):
     synchronised once.  Returns the ``verify.CertCheck`` (``.ok`` is the list
     of bool).  A record the buffer ends before decodes to zero bytes (unmarshal
     status 1): its zero signature verifies as BAD_RS, so it is *not valid* to
-    the check."""
+    the check.
+
+    With ``sets`` (a ``verify.SignatorySets``) certificate k is decided under
+    set ``set_of[k]`` of it (``set_of=None``: each CertSpec's ``set``): upload
+    -> unmarshal -> hd_verify_batch_device for the verdicts ->
+    hd_check_certificates_sets_device, again on one stream with one
+    synchronisation, and the verifier's own set decides nothing."""
     import numpy as np
     import torch
     from . import codec
@@ -142,6 +160,12 @@ def check_certificates_wire(verifier, kind, buf, certs):
         d_bitmap = torch.zeros((n + 31) // 32 + 1, dtype=torch.int32, device="cuda")
     if n:
         codec.unmarshal_device(verifier, mtype, d_buf[: raw.numel()], n, with_sig=True, stream=ws, sync=False, out=db)
+    if sets is not None:
+        if n:
+            verifier.verify_batch_device(db.c_struct(), d_verdict.data_ptr(), None, None, None, ws.cuda_stream)
+        return verifier.check_certificates_sets_device(db.c_struct(), d_verdict.data_ptr(), certs, sets, set_of,
+                                                       ws.cuda_stream)
+    if n:
         verifier.verify_batch_device(db.c_struct(), d_verdict.data_ptr(), None, d_signer.data_ptr(),
                                      d_bitmap.data_ptr(), ws.cuda_stream)
     return verifier.check_certificates_device(db.c_struct(), d_bitmap.data_ptr(), d_signer.data_ptr(),

@@ -713,7 +713,8 @@ class DeviceSelection:
 
 # statuses of check_certificates (include/hd_cert.h HD_CERT_*)
 CERT_OK, CERT_SHORT, CERT_BAD_SIGNATURE, CERT_WRONG_FIELD, CERT_REPEATED_SENDER = 0, 1, 2, 3, 4
-CERT_NAMES = ["OK", "SHORT", "BAD_SIGNATURE", "WRONG_FIELD", "REPEATED_SENDER"]
+CERT_NOT_MEMBER = 5   # check_certificates_sets only: authentic, but From is outside the certificate's set
+CERT_NAMES = ["OK", "SHORT", "BAD_SIGNATURE", "WRONG_FIELD", "REPEATED_SENDER", "NOT_MEMBER"]
 
 
 @dataclass
@@ -721,7 +722,9 @@ class CertSpec:
     """One certificate to check (hd_cert): messages [first, first + count) of
     a batch must be VALID votes of ``kind`` ("prevote" / "precommit", or the
     type) for ``value`` at (height, round), from pairwise distinct
-    signatories, at least ``quorum`` (2f+1) of them."""
+    signatories, at least ``quorum`` (2f+1) of them.  ``set``: the id of the
+    signatory set (SignatorySets.add) the certificate falls under, read by
+    check_certificates_sets when it is given no ``set_of``."""
     first: int
     count: int
     kind: object
@@ -729,6 +732,7 @@ class CertSpec:
     round: int
     value: bytes
     quorum: int
+    set: Optional[int] = None
 
 
 @dataclass
@@ -766,6 +770,79 @@ def cert_rows(certs):
         row.height, row.round = int(c.height), int(c.round)
         ctypes.memmove(row.value32, value, 32)
     return rows
+
+
+def cert_sets(certs, set_of, k: int) -> np.ndarray:
+    """The set id of every certificate as uint32[k]: ``set_of``, or each
+    CertSpec's ``set``."""
+    if set_of is None:
+        if isinstance(certs, ctypes.Array) or any(c.set is None for c in certs):
+            raise ValueError("set_of, or a set in every CertSpec")
+        set_of = [c.set for c in certs]
+    ids = np.ascontiguousarray(set_of, np.int64)
+    if ids.shape != (k,) or (k and (ids.min() < 0 or ids.max() > 0xFFFFFFFF)):
+        raise ValueError("one set id per certificate")
+    return ids.astype(np.uint32)
+
+
+class SignatorySets:
+    """Signatory sets resident on the device, apart from the verifier's
+    admitted set (include/hd_sigsets.h): ``add`` at each ResetHeight a peer
+    learns of, then check_certificates_sets decides every certificate under
+    the set it names.  Nothing here touches set_signatories' set."""
+
+    def __init__(self, v: "Verifier"):
+        self._v = v
+        self._lib = v._lib
+        h = ctypes.c_void_p()
+        v._check(self._lib.hd_sigsets_create(v.handle, ctypes.byref(h)), "hd_sigsets_create")
+        self._sets = h
+        self._close_rank = 0          # closed before its Verifier (either order is allowed)
+        _lib.track(self)
+
+    def close(self):
+        if getattr(self, "_sets", None):
+            self._lib.hd_sigsets_destroy(self._sets)
+            self._sets = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    @property
+    def handle(self):
+        return self._sets
+
+    def _check(self, rc: int, where: str):
+        if rc != 0:
+            raise HDError(rc, where)
+
+    def add(self, signatories) -> int:
+        """hd_sigsets_add: one more set (n x 32 bytes, any order, duplicates
+        allowed, n = 0 allowed); returns its id.  Earlier ids stay valid."""
+        arr = _as_rows(signatories, 32)
+        sid = ctypes.c_uint32()
+        self._check(self._lib.hd_sigsets_add(self._sets, _ptr(arr) if len(arr) else None, len(arr), ctypes.byref(sid)),
+                    "hd_sigsets_add")
+        return int(sid.value)
+
+    def clear(self) -> None:
+        self._check(self._lib.hd_sigsets_clear(self._sets), "hd_sigsets_clear")
+
+    def info(self, set_id: int) -> Tuple[int, int]:
+        """(rows given to add, distinct rows) of a set"""
+        r, d = ctypes.c_uint32(), ctypes.c_uint32()
+        self._check(self._lib.hd_sigsets_info(self._sets, int(set_id), ctypes.byref(r), ctypes.byref(d)),
+                    "hd_sigsets_info")
+        return int(r.value), int(d.value)
 
 
 def _cert_check(res, k: int, verdict=None) -> CertCheck:
@@ -1081,6 +1158,42 @@ class Verifier:
         self._check(self._lib.hd_check_certificates_device(self._ctx, ctypes.byref(dbatch), d_bitmap, d_signer,
                                                            int(n_signers), rows, k, res, stream),
                     "hd_check_certificates_device")
+        return _cert_check(res, k)
+
+    def open_sets(self) -> SignatorySets:
+        """An empty collection of signatory sets on this context (hd_sigsets)."""
+        return SignatorySets(self)
+
+    def check_certificates_sets(self, batch: Batch, certs, sets: SignatorySets, set_of=None,
+                                verdict: bool = False) -> CertCheck:
+        """hd_check_certificates_sets: as check_certificates, with certificate
+        k decided under set ``set_of[k]`` of ``sets`` (or its CertSpec's
+        ``set``) instead of this verifier's signatory set, which the call
+        leaves alone.  A message whose signature is its From's but whose From
+        is outside the certificate's set makes the status CERT_NOT_MEMBER."""
+        rows = cert_rows(certs)
+        k = len(rows)
+        ids = cert_sets(certs, set_of, k)
+        res = (_lib.HdCertResult * max(k, 1))()
+        vd = np.zeros(len(batch), np.uint8) if verdict else None
+        cb = batch.c_struct()
+        self._check(self._lib.hd_check_certificates_sets(self._ctx, sets.handle, ctypes.byref(cb), rows, _ptr(ids), k,
+                                                         res, _ptr(vd)), "hd_check_certificates_sets")
+        return _cert_check(res, k, vd)
+
+    def check_certificates_sets_device(self, dbatch: HdBatch, d_verdict: int, certs, sets: SignatorySets,
+                                       set_of=None, stream: Optional[int] = None) -> CertCheck:
+        """hd_check_certificates_sets_device: the batch on the device (type,
+        height, round, value and From are read) and the verdict bytes
+        verify_batch_device or authenticate_batch_device wrote for it.  Queued
+        on ``stream`` behind the verification, which is synchronised once."""
+        rows = cert_rows(certs)
+        k = len(rows)
+        ids = cert_sets(certs, set_of, k)
+        res = (_lib.HdCertResult * max(k, 1))()
+        self._check(self._lib.hd_check_certificates_sets_device(self._ctx, sets.handle, ctypes.byref(dbatch), d_verdict,
+                                                                rows, _ptr(ids), k, res, stream),
+                    "hd_check_certificates_sets_device")
         return _cert_check(res, k)
 
     @staticmethod

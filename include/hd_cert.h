@@ -27,6 +27,7 @@
 #ifndef HD_CERT_H
 #define HD_CERT_H
 
+#include "hd_sigsets.h"
 #include "hd_verify.h"
 
 #ifdef __cplusplus
@@ -38,6 +39,8 @@ extern "C" {
 #define HD_CERT_BAD_SIGNATURE    2   /* lowest offending message is not VALID */
 #define HD_CERT_WRONG_FIELD      3   /* ... has another type, height, round or value */
 #define HD_CERT_REPEATED_SENDER  4   /* ... repeats the signatory of a lower clean message */
+#define HD_CERT_NOT_MEMBER       5   /* hd_check_certificates_sets only: lowest offending message is
+                                        authentic, its From outside the certificate's set */
 
 typedef struct {            /* 64 bytes */
     uint32_t first, count;  /* messages [first, first + count) of the batch */
@@ -99,6 +102,64 @@ typedef struct {
     uint64_t scratch_bytes;  /* blocks * slice_bytes */
 } hd_cert_plan;
 int hd_cert_plan_info(uint32_t n_signers, uint32_t K, hd_cert_plan* plan);
+
+/* ---- several signatory sets in one call -----------------------------------
+ * A peer that has fallen behind receives certificates for many heights, and
+ * the reference rebuilds procsAllowed at every ResetHeight
+ * (replica/replica.go:136-144): those certificates fall under several
+ * signatory sets.  Here certificate k is checked under set set_of[k] of an
+ * hd_sigsets (hd_sigsets.h), not under the context's admitted set, which the
+ * call neither reads for membership nor changes.
+ *
+ * Semantics.  Each message of a segment has exactly one class, tested in this
+ * order:
+ *   1. not authentic: its verdict byte is neither HD_VERDICT_VALID nor
+ *                     HD_VERDICT_NOT_ADMITTED (the two the ingress treats as
+ *                     authenticated: the signature is From's, whatever the
+ *                     context's set says about From)
+ *   2. not a member:  its from32 is not an entry of set set_of[k]
+ *   3. wrong field:   type, height, round or value32 differs from the
+ *                     certificate's
+ *   4. repeat:        a clean message with a lower index in the same segment
+ *                     has the same From -- the same position in the set's
+ *                     sorted distinct rows (clean: authentic, a member and
+ *                     matching the fields)
+ * Classes 1-4 are offending.  good, first_bad and SHORT are exactly as above;
+ * status is SHORT when count < quorum, otherwise the class of message
+ * first_bad (BAD_SIGNATURE, NOT_MEMBER, WRONG_FIELD, REPEATED_SENDER),
+ * otherwise OK.  A message that is not clean never makes a later message a
+ * repeat.  Certificates of different sets may overlap and come in any order;
+ * an empty set makes every authentic message NOT_MEMBER.  Every output is a
+ * pure function of the inputs.
+ *
+ * The per-signer table has one word per distinct entry of the certificate's
+ * set; its placement (hd_cert_plan_info) is decided once per call, by the
+ * largest distinct count among the sets the call names.
+ *
+ * Device form.  dbatch (type, height, round, value32 and from32 are read) and
+ * d_verdict, the n verdict bytes hd_verify_batch_device or
+ * hd_authenticate_batch_device wrote for that batch.  certs, set_of and
+ * results are host arrays of K rows.  One upload of the K rows and their K set
+ * ids on `stream` (NULL: the context's), one launch, one download, one
+ * synchronisation.  There is no bitmap and no signer array: a signer index
+ * names a row of one admitted set and means nothing across sets.
+ * HD_EINVAL, before any device work and with `results` untouched, for what
+ * hd_check_certificates_device refuses (d_verdict in the place of the bitmap),
+ * a NULL sets, set_of or from32, a set_of[k] that `sets` does not hold, `sets`
+ * created on another context, or a value32 or from32 that is not 16-byte
+ * aligned.  K == 0 is HD_OK.  One call at a time per context, as above. */
+int hd_check_certificates_sets_device(hd_ctx* ctx, const hd_sigsets* sets, const hd_batch* dbatch,
+                                      const uint8_t* d_verdict, const hd_cert* certs, const uint32_t* set_of,
+                                      uint32_t K, hd_cert_result* results, void* stream);
+
+/* Host form: one upload of `batch`, hd_verify_batch_device for the verdicts
+ * only -- against whatever set the context has: VALID and NOT_ADMITTED are both
+ * authentic -- then the same check on the context's stream; the only
+ * synchronisation is the download.  verdict: n bytes (HD_VERDICT_*) or NULL; it
+ * tells why a BAD_SIGNATURE message failed.  Errors as the device form, plus
+ * HD_EINVAL for a NULL column of a batch of n > 0. */
+int hd_check_certificates_sets(hd_ctx* ctx, const hd_sigsets* sets, const hd_batch* batch, const hd_cert* certs,
+                               const uint32_t* set_of, uint32_t K, hd_cert_result* results, uint8_t* verdict);
 
 #ifdef __cplusplus
 }
