@@ -18,8 +18,10 @@ struct HdVarRow {
 inline const HdVarRow HD_VARIANTS[HD_VAR__COUNT] = {
     {HD_VAR_VERIFY_WAVES, "HD_VERIFY_WAVES", 3, 2, 4, nullptr},
     {HD_VAR_SUM_WAVES, "HD_SUM_WAVES", 0, 0, 0, [](int v) { return v == 0 || (v >= 2 && v <= 4); }},
-    {HD_VAR_SUM_PREFETCH, "HD_SUM_PF", 1, 1, 2, nullptr},
-    {3, nullptr, 0, 1, 0, nullptr},   // keys 3, 6: removed in round 5 (no gain measured); set rejects, get reads
+    // key 2 (k_fast_sums prefetch depth; 2 spilt and lost) and keys 3, 6 (round 5: no
+    // gain measured) are retired: set rejects, get reads
+    {2, nullptr, 1, 1, 0, nullptr},
+    {3, nullptr, 0, 1, 0, nullptr},
     {HD_VAR_SPLIT_K, "HD_FAST_K", -1, 0, 0, [](int v) { return v == -1 || v == 8 || v == 16; }},
     {HD_VAR_RECOVER_G, "HD_RECOVER_GLV_G", 0, 0, 1, nullptr},   // (the variable's presence means 1: hd_ctx_create)
     {6, nullptr, 2, 1, 0, nullptr},
@@ -55,8 +57,11 @@ struct FbPlanIn {
 
 // Everything decided per call (but the window width, FbWork::wp, and the capped block's LDS bytes).
 struct FbCallPlan {
-    int k, waves;              // messages per inversion (8 or 16); k_fast_sums waves per SIMD asked for (2, 3, 4)
-    int sums_waves, sums_pf;   // the k_fast_sums<WAVES, WP, PF> launched
+    int k, waves;     // messages per inversion (8 or 16); k_fast_sums waves per SIMD asked for (2, 3, 4)
+    // The k_fast_sums<WAVES, WP> launched: sums_waves alone names the form.  sums_pf reports the prefetch
+    // depth that form has (0 or 1, as the kernel derives it from WAVES) to the host build's plan export
+    // (hdh_fb_plan, tests/native/hd_host_check.cpp), whose layout the plan tests read; no launch reads it.
+    int sums_waves, sums_pf;
     bool overlap, capped, lean, chain, share, dedup, lift;   // (capped, lean and chain need overlap)
     uint32_t full, lift_blocks, slow_blocks;   // fallback grids: over the whole batch, k_slow_lift's, k_verify's
 };
@@ -121,11 +126,8 @@ inline FbCallPlan fb_plan_call(const FbPlanIn& in) {
     p.capped = var[HD_VAR_SUM_CAP] && p.overlap && p.waves == 3;
     p.lean = var[HD_VAR_LEAN_INV] && p.overlap;
     p.chain = var[HD_VAR_SUM_CHAIN] && p.overlap;
-    // prefetch depth 2 has a 2- and a 3-wave form only (a 4-wave choice takes
-    // the 3-wave one, uncapped); the 4-wave form loads its points when used
-    const bool pf2 = var[HD_VAR_SUM_PREFETCH] == 2;
-    p.sums_waves = p.waves == 2 ? 2 : pf2 || p.waves != 4 ? 3 : 4;
-    p.sums_pf = pf2 ? 2 : p.sums_waves == 4 ? 0 : 1;
+    p.sums_waves = p.waves;
+    p.sums_pf = p.sums_waves == 4 ? 0 : 1;   // the 4-wave form loads its points when used
     p.share = var[HD_VAR_PRE_SHARE] && !in.caller_digests;
     p.dedup = var[HD_VAR_DEDUP] != 0;
     p.lift = var[HD_VAR_SLOW_LIFT] != 0;

@@ -34,7 +34,7 @@ struct DevBuf {
 
 struct TallyWork;  // hd_tally.hip
 struct HostPipe;   // hd_host.hip: hd_verify_submit pipelines
-struct FbWork;     // hd_fastverify.hip: known-key tables and fast-path scratch
+struct FbWork;     // hd_fbwork.h: known-key tables and fast-path scratch
 struct CertWork;   // hd_certcheck.hip: the certificate check's rows and table scratch
 
 struct hd_ctx {
@@ -139,7 +139,7 @@ int hd_decide_run(hd_ctx* ctx, const hd_batch* hb, const uint8_t* d_verdict, con
                   hd_decide_out* out, hipStream_t s, hd_decide_order* ord, const DecideExt* ext,
                   hd_catch_out* caught);
 
-// known-key fast path (hd_fastverify.hip)
+// known-key fast path (tables and slots: hd_fbtables.hip; a verify call: hd_fastverify.hip)
 int hd_fb_init(hd_ctx* ctx);                    // tables of G (slot 0); at context creation
 void hd_fb_release(hd_ctx* ctx);
 const hd::gp* hd_fb_gtab(const hd_ctx* ctx);    // the shared fixed-base G table (NULL: none)
@@ -200,7 +200,7 @@ struct SlowCtl {
     uint32_t* fnext;
     uint32_t fbase, fcap;
     uint32_t* fpend;          // host-mapped: the claim count, so the host builds the new tables
-    // slot eviction (hd_fastverify.hip fb_evict): a From the dictionary holds
+    // slot eviction (hd_fbtables.hip fb_evict): a From the dictionary holds
     // without a slot keeps its key in fkey[bucket] and counts its recoveries
     // in fbhit[bucket]; fmiss (host-mapped) is set on every such recovery
     uint32_t* fbhit;

@@ -1,16 +1,17 @@
-// hd_inv2.h -- the lean inversions of the known-key check in two levels
-// (hd_fastverify.hip): the lean walk of k_fast_sinv_lean /
-// k_fast_zinv_lean cut at its inversion into three passes, and the same walk
-// applied a second time to the lanes' own products, so that one divstep
-// inversion serves K * K2 slots instead of K.
+// hd_inv2.h -- the lean inversions of the known-key check (hd_fastinv.hip,
+// DESIGN.md §4).  In one level (inv2_lean: k_fast_sinv_lean /
+// k_fast_zinv_lean) a lane walks up its K slots, inverts its product and
+// walks back down.  In two levels the same walk is cut at its inversion into
+// three passes, and applied a second time to the lanes' own products, so that
+// one divstep inversion serves K * K2 slots instead of K.
 //
 //   up    lane t < T: prefix products of its K slots j T + t into the pre
-//         row (today's first loop), then the lane's product as root t; a
-//         lane without a live slot stores the domain's identity
+//         row (inv2_walk_up), then the lane's product as root t; a lane
+//         without a live slot stores the domain's identity
 //   mid   lane u < T2 = split_lanes<K2>(T): the same walk over the roots
 //         j T2 + u < T, prefixes through the roots-prefix row, ONE
 //         inversion, and on the way back each root's inverse in its place
-//   down  lane t < T: today's second loop, inv loaded from root t
+//   down  lane t < T: inv2_walk_down, inv loaded from root t
 //
 // Every root below T is a value of the domain (a product or the identity), so
 // the middle level needs no marker: its live roots are exactly those below
@@ -78,13 +79,13 @@ HD bool inv2_live(const uint32_t* __restrict__ aux, uint32_t nc, uint32_t i) {
     return i < nc && (aux[i] & 0xFFu) == HD_FAST_LIVE;
 }
 
-// up, lane t < T over slots j T + t (rows of stride n): the prefix products
-// of the live slots into pre, the lane's product (or the identity) to root t
+// The walk up, lane t < T over slots j T + t (rows of stride n): the prefix
+// products of the live slots into pre.  Returns the mask of the live slots
+// (bit j) and leaves the lane's product in acc (0 when no slot is live).
 template <class E, int K>
-HD void inv2_up(uint32_t t, uint32_t T, uint32_t nc, uint32_t n, const uint32_t* __restrict__ aux,
-                const uint32_t* __restrict__ in, uint32_t* __restrict__ pre, uint32_t* __restrict__ roots) {
+HD uint32_t inv2_walk_up(E& acc, uint32_t t, uint32_t T, uint32_t nc, uint32_t n, const uint32_t* __restrict__ aux,
+                         const uint32_t* __restrict__ in, uint32_t* __restrict__ pre) {
     uint32_t live = 0;
-    E acc;
     HD_UNROLL for (int k = 0; k < 9; k++) acc.n[k] = 0;
     HD_NOUNROLL for (int j = 0; j < K; j++) {
         const uint32_t i = (uint32_t)j * T + t;
@@ -96,7 +97,51 @@ HD void inv2_up(uint32_t t, uint32_t T, uint32_t nc, uint32_t n, const uint32_t*
         live |= 1u << j;
         soa_store(pre, n, i, acc.n);   // the product of the live slots up to j
     }
-    if (!live) inv2_one(acc);
+    return live;
+}
+
+// The walk back, from inv = the inverse (as inv2_inv gives it) of the product
+// of the slots in `live`: each live slot's inverse into pre.
+template <class E, int K>
+HD void inv2_walk_down(E inv, uint32_t live, uint32_t t, uint32_t T, uint32_t n, const uint32_t* __restrict__ in,
+                       uint32_t* __restrict__ pre) {
+    HD_NOUNROLL for (int j = K - 1; j >= 0; j--) {
+        if (!((live >> j) & 1u)) continue;
+        const uint32_t i = (uint32_t)j * T + t;
+        const uint32_t below = live & ((1u << j) - 1u);
+        if (below) {   // a live slot before this one: the highest such holds the prefix
+            const uint32_t ip = (uint32_t)(31 - __builtin_clz(below)) * T + t;
+            E pp, x, xi;
+            soa_load(pp.n, pre, n, ip);
+            inv2_leaf(x, in, n, i);
+            inv2_mul(xi, inv, pp);
+            inv2_mul(inv, inv, x);
+            soa_store(pre, n, i, xi.n);
+        } else {
+            soa_store(pre, n, i, inv.n);
+        }
+    }
+}
+
+// The lean inversion in one level (k_fast_sinv_lean / k_fast_zinv_lean), lane
+// t < T: up, one inversion per lane, back down with the mask the walk up
+// returned.  A lane without a live slot stores nothing.
+template <class E, int K>
+HD void inv2_lean(uint32_t t, uint32_t T, uint32_t nc, uint32_t n, const uint32_t* __restrict__ aux,
+                  const uint32_t* __restrict__ in, uint32_t* __restrict__ pre) {
+    E acc, inv;
+    const uint32_t live = inv2_walk_up<E, K>(acc, t, T, nc, n, aux, in, pre);
+    if (!live) return;
+    inv2_inv(inv, acc);
+    inv2_walk_down<E, K>(inv, live, t, T, n, in, pre);
+}
+
+// up, lane t < T: the walk up, then the lane's product (or the identity) to root t
+template <class E, int K>
+HD void inv2_up(uint32_t t, uint32_t T, uint32_t nc, uint32_t n, const uint32_t* __restrict__ aux,
+                const uint32_t* __restrict__ in, uint32_t* __restrict__ pre, uint32_t* __restrict__ roots) {
+    E acc;
+    if (!inv2_walk_up<E, K>(acc, t, T, nc, n, aux, in, pre)) inv2_one(acc);
     soa_store(roots, T, t, acc.n);
 }
 
@@ -145,22 +190,7 @@ HD void inv2_down(uint32_t t, uint32_t T, uint32_t nc, uint32_t n, const uint32_
     if (!live) return;
     E inv;
     soa_load(inv.n, roots, T, t);
-    HD_NOUNROLL for (int j = K - 1; j >= 0; j--) {
-        if (!((live >> j) & 1u)) continue;
-        const uint32_t i = (uint32_t)j * T + t;
-        const uint32_t below = live & ((1u << j) - 1u);
-        if (below) {   // a live slot before this one: the highest such holds the prefix
-            const uint32_t ip = (uint32_t)(31 - __builtin_clz(below)) * T + t;
-            E pp, x, xi;
-            soa_load(pp.n, pre, n, ip);
-            inv2_leaf(x, in, n, i);
-            inv2_mul(xi, inv, pp);
-            inv2_mul(inv, inv, x);
-            soa_store(pre, n, i, xi.n);
-        } else {
-            soa_store(pre, n, i, inv.n);
-        }
-    }
+    inv2_walk_down<E, K>(inv, live, t, T, n, in, pre);
 }
 
 }  // namespace hd

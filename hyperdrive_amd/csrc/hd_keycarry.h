@@ -1,5 +1,5 @@
 // hd_keycarry.h -- which known keys a set change keeps when it re-tiers the
-// key tables (hd_fastverify.hip fb_map; DESIGN.md §4 "Where P comes from"):
+// key tables (hd_fbtables.hip fb_map; DESIGN.md §4 "Where P comes from"):
 // plain C++, no HIP, so the slot plan is tested without a GPU
 // (tests/native/hd_keycarry_check.cpp runs this same text).
 //

@@ -1,6 +1,6 @@
 // hd_keyimport.hip -- hd_import_keys / hd_export_keys (include/hd_verify.h):
 // the caller-driven way into, and out of, the key slots of the known-key
-// fast path (hd_fastverify.hip; DESIGN.md §4 "Where P comes from").
+// fast path (hd_fbtables.hip; DESIGN.md §4 "Where P comes from").
 //
 // Import, on the context's stream after the context is quiesced:
 //   k_key_import   one key per lane (hd_keyimport.h key_classify): on the
@@ -17,7 +17,7 @@
 //
 // The key carry (hd_keycarry.h) lives here too: k_key_gather and k_key_carry
 // take the known keys over a set change that frees the tables (fb_map in
-// hd_fastverify.hip calls hd_key_stash_*).  Those keys stay on the device.
+// hd_fbtables.hip calls hd_key_stash_*).  Those keys stay on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

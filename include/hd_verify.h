@@ -212,7 +212,7 @@ int hd_ctx_fastpath_stats(hd_ctx* ctx, uint32_t* known_keys, uint32_t* last_fall
 /* Foreign-key slots (HD_VAR_FOREIGN_KEYS): ready_slots = foreign slots whose
  * tables are built; evictions = slotless Froms promoted so far into the slot
  * of a colder foreign key (a From with more recoveries since the last check
- * than twice the slot holder's known-key checks + 4; hd_fastverify.hip
+ * than twice the slot holder's known-key checks + 4; hd_fbtables.hip
  * fb_evict); checks = eviction checks so far (each waited for the context's
  * earlier verify calls).  Any may be NULL; synchronises the context's calls. */
 int hd_ctx_foreign_stats(hd_ctx* ctx, uint32_t* ready_slots, uint32_t* evictions, uint32_t* checks);
@@ -281,7 +281,6 @@ int hd_ctx_profile(hd_ctx* ctx, int enable);
                                    pubkeys; the other formats run the 3-wave build) [HD_VERIFY_WAVES] */
 #define HD_VAR_SUM_WAVES 1      /* k_fast_sums waves per SIMD: 2, 3 or 4 (128 VGPRs, table points loaded when
                                    used); 0 (default) 4 for batches under two rounds at 3, else 3 [HD_SUM_WAVES] */
-#define HD_VAR_SUM_PREFETCH 2   /* k_fast_sums table-point prefetch depth: 1 (default) or 2 [HD_SUM_PF] */
 #define HD_VAR_SPLIT_K 4        /* messages per inversion of the known-key check: -1 by the number of distinct
                                    checked messages (default), 8 or 16 [HD_FAST_K] */
 #define HD_VAR_RECOVER_G 5      /* the full recovery's u1 G: 0 from the fixed-base G table (default), 1 from the
@@ -343,7 +342,10 @@ int hd_ctx_profile(hd_ctx* ctx, int enable);
 /* Keys 3 and 6 (the digit pass and the paired kernel's waves) were measured
  * without gain and removed in round 5: set returns HD_EINVAL for them, get
  * returns their fixed value.  (The cap, the lean inversions and the chain,
- * removed with them, came back in round 12 under their old keys.) */
+ * removed with them, came back in round 12 under their old keys.)  Key 2,
+ * k_fast_sums' table-point prefetch depth, went the same way: depth 2 spilt
+ * and measured 1-3 % slower, so the depth is fixed
+ * (one addition ahead; the 4-wave form loads when used) and get returns 1. */
 #define HD_VAR__COUNT 16
 int hd_ctx_set_variant(hd_ctx* ctx, int which, int value);
 int hd_ctx_get_variant(hd_ctx* ctx, int which, int* value);

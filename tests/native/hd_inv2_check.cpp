@@ -1,8 +1,9 @@
-// hd_inv2_check.cpp -- host check of the two-level lean inversions
+// hd_inv2_check.cpp -- host check of the lean inversions
 // (hyperdrive_amd/csrc/hd_inv2.h): the up, mid and down passes the gfx950
 // kernels run, lane by lane over plain arrays, for both domains (scalars
 // mod n in Montgomery form, field elements mod p), K in {8, 16} x K2 in
-// {8, 16}, against a direct divstep inversion of every live entry.
+// {8, 16}, against a direct divstep inversion of every live entry; then the
+// one-level walk (inv2_lean) over the same inputs, checked the same way.
 //
 // Sizes N: 1, 64 K, 64 K + 1, 64 K K2 + 1 (the first with a second wave of
 // inverting lanes).  Live masks: random, whole level-1 lanes dead, whole
@@ -152,20 +153,32 @@ static long run(const Pool<Dom>& pool, uint32_t N, int mask) {
     for (uint32_t t = 0; t < T; t++) inv2_up<D, K>(t, T, nc, n, aux.data(), in.data(), pre.data(), roots.data());
     for (uint32_t u = 0; u < T2; u++) inv2_mid<D, K2>(u, T2, T, roots.data(), rpre.data());
     for (uint32_t t = 0; t < T; t++) inv2_down<D, K>(t, T, nc, n, aux.data(), in.data(), pre.data(), roots.data());
-    long checked = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        uint32_t e[9];
-        for (int k = 0; k < 9; k++) e[k] = pre[(size_t)k * n + i];
-        if (i < nc && live[i]) {
-            uint32_t got[8];
-            Dom::canon(got, e);
-            if (memcmp(got, &pool.inv[(size_t)i * 8], 32)) fail("inverse differs", Dom::name(), K, K2, N, mask, i);
-            checked++;
-        } else {
-            for (int k = 0; k < 9; k++)
-                if (e[k] != POISON) fail("a dead entry was written", Dom::name(), K, K2, N, mask, i);
+    // every live entry's inverse against the direct one, every dead entry's
+    // pre words untouched; what[]: the two failures' names
+    auto check = [&](const char* const what[2]) {
+        long checked = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            uint32_t e[9];
+            for (int k = 0; k < 9; k++) e[k] = pre[(size_t)k * n + i];
+            if (i < nc && live[i]) {
+                uint32_t got[8];
+                Dom::canon(got, e);
+                if (memcmp(got, &pool.inv[(size_t)i * 8], 32)) fail(what[0], Dom::name(), K, K2, N, mask, i);
+                checked++;
+            } else {
+                for (int k = 0; k < 9; k++)
+                    if (e[k] != POISON) fail(what[1], Dom::name(), K, K2, N, mask, i);
+            }
         }
-    }
+        return checked;
+    };
+    const char* const two[2] = {"inverse differs", "a dead entry was written"};
+    const long checked = check(two);
+    // the one-level walk (inv2_lean: k_fast_sinv_lean / k_fast_zinv_lean) on the same inputs
+    pre.assign(pre.size(), POISON);
+    for (uint32_t t = 0; t < T; t++) inv2_lean<D, K>(t, T, nc, n, aux.data(), in.data(), pre.data());
+    const char* const one[2] = {"one level: inverse differs", "one level: a dead entry was written"};
+    if (check(one) != checked) fail("one level: entries checked", Dom::name(), K, K2, N, mask, checked);
     return checked;
 }
 

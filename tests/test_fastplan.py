@@ -10,13 +10,15 @@ import itertools
 import pytest
 
 NONE = 0xFFFFFFFF
-KEY = {"verify_waves": 0, "sum_waves": 1, "sum_prefetch": 2, "split_k": 4, "recover_g": 5, "key_width": 7,
+KEY = {"verify_waves": 0, "sum_waves": 1, "split_k": 4, "recover_g": 5, "key_width": 7,
        "wave_prio": 8, "sum_cap": 9, "foreign_keys": 10, "slow_lift": 11, "dedup": 12, "lean_inv": 13,
        "sum_chain": 14, "pre_share": 15}
-DEFAULTS = {"verify_waves": 3, "sum_waves": 0, "sum_prefetch": 1, "split_k": -1, "recover_g": 0, "key_width": 0,
+DEFAULTS = {"verify_waves": 3, "sum_waves": 0, "split_k": -1, "recover_g": 0, "key_width": 0,
             "wave_prio": 0, "sum_cap": 1, "foreign_keys": 16, "slow_lift": 1, "dedup": 1, "lean_inv": 1,
             "sum_chain": 1, "pre_share": 1}
-REMOVED = {3: 0, 6: 2}   # removed in round 5: key -> the value get still returns
+# removed (3, 6 in round 5; 2, the sums' prefetch depth, once depth 2 had lost every A/B): key -> the value get
+# still returns
+REMOVED = {2: 1, 3: 0, 6: 2}
 SWITCHES = ("recover_g", "sum_cap", "slow_lift", "dedup", "lean_inv", "sum_chain", "pre_share")
 
 
@@ -81,16 +83,21 @@ def test_capped_lean_chain_follow_their_variants_on_the_overlap_path(hostmath):
     assert (off["overlap"], off["capped"], off["lean"], off["chain"]) == (0, 0, 0, 0)
 
 
-@pytest.mark.parametrize("waves,pf,form", [(2, 1, (2, 1)), (3, 1, (3, 1)), (4, 1, (4, 0)),
-                                           (2, 2, (2, 2)), (3, 2, (3, 2)), (4, 2, (3, 2))])
+# (waves asked for, the retired key 2's fixed value, the form: k_fast_sums' WAVES and the prefetch depth that
+# form has -- 0 for the 4-wave form, which loads its points when used, else 1)
+@pytest.mark.parametrize("waves,pf,form", [(2, 1, (2, 1)), (3, 1, (3, 1)), (4, 1, (4, 0))])
 def test_sums_form(hostmath, waves, pf, form):
-    p = plan(hostmath, 393216, sum_waves=waves, sum_prefetch=pf)
+    assert hostmath.variant(2, pf)[:2] == (pf, False)   # get reads 1, set rejects even that
+    p = plan(hostmath, 393216, sum_waves=waves)
     assert p["waves"] == waves and (p["sums_waves"], p["sums_pf"]) == form
     assert p["capped"] == (1 if waves == 3 else 0)
     # the rule's own choice of 4 and of 3 waves takes the same forms
-    auto = plan(hostmath, 393215 if waves == 4 else 393216, sum_prefetch=pf)
+    auto = plan(hostmath, 393215 if waves == 4 else 393216)
     if waves != 2:
         assert auto["waves"] == waves and (auto["sums_waves"], auto["sums_pf"]) == form
+    # whatever key 2 of a variant vector holds, the plan is the same
+    var = [3, waves, 2, 0, -1, 0, 2, 0, 0, 1, 16, 1, 1, 1, 1, 1]
+    assert hostmath.fb_plan(var, 256, 393216, False, False, (NONE,) * 4) == p
 
 
 def test_share_dedup_lift(hostmath):
@@ -134,7 +141,7 @@ def test_variant_accepted_values(hostmath):
         assert not any(hostmath.variant(key, v)[1] for v in range(-2, 70))
     assert accepted("verify_waves", -2, 8) == [2, 3, 4]
     assert accepted("sum_waves", -2, 8) == [0, 2, 3, 4]
-    assert accepted("sum_prefetch", -2, 8) == [1, 2]
+    assert [v for v in range(-2, 9) if hostmath.variant(2, v)[1]] == []   # the prefetch depth: retired
     assert accepted("split_k", -3, 40) == [-1, 8, 16]
     assert accepted("wave_prio", -2, 8) == [0, 1, 2, 3]
     assert accepted("foreign_keys", -2, 70) == list(range(0, 65))

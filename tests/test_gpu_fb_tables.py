@@ -1,5 +1,5 @@
 """The fixed-base tables the device builds for itself (k_fb_bases / k_fb_runs,
-hd_fastverify.hip), read back entry by entry through hd_fb_table_read and
+hd_fbtables.hip), read back entry by entry through hd_fb_table_read and
 compared with Python integers (tests/fb_table_ref.py), all 64 bytes of every
 entry, no tolerance.
 

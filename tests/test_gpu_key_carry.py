@@ -1,5 +1,5 @@
 """A set change that re-tiers the key tables keeps the known keys (fb_map in
-hd_fastverify.hip, the plan of hd_keycarry.h, k_key_gather / k_key_carry in
+hd_fbtables.hip, the plan of hd_keycarry.h, k_key_gather / k_key_carry in
 hd_keyimport.hip), on the GPU.
 
 Width arithmetic the cases rest on (fb_pick_width, fb_slot_bytes):

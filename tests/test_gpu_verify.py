@@ -286,7 +286,7 @@ def test_foreign_slot_eviction(gpu, coracle):
     slots, 4 throwaway Froms (one NOT_ADMITTED message each) claim them first;
     a fifth foreign sender with many messages then counts recoveries while it
     has no slot, and a later call hands it the slot of the coldest throwaway
-    key (hd_fastverify.hip fb_evict), after which its messages take the
+    key (hd_fbtables.hip fb_evict), after which its messages take the
     known-key check.  Every call's verdicts and recovered signatories equal
     the C oracle; the throwaway keys' messages stay exact after losing their
     slots."""
